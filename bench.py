@@ -13,8 +13,11 @@ the barrier and the max-over-ranks of the timings go over a Unix socket among th
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) re-executes itself under torch.distributed.run with N ranks;
 it refuses to run when fewer than N GPUs are visible instead of reporting a 1-GPU number.
 
-The timed region is `--repeats` (default 5) back-to-back measurements of EXACTLY `--steps` steps each, every one bracketed by
-barrier + synchronize; `value` / `ms_per_step` are the MEDIAN repeat, the spread is reported in `repeats`.
+The timed region is EXACTLY `--steps` steps, bracketed by barrier + synchronize; `ms_per_step` is the time of one of them.  `--repeats R`
+(default 1) times R such back-to-back measurements instead; `value` / `ms_per_step` are then the MEDIAN repeat, the spread is reported in `repeats`.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (key points, descriptors, matches12 of a fixed sample of camera
+slots) as DIR/<name>.npy, float32 / float64, so that two builds run with the same arguments (the inputs are seeded) can be compared.
 
 Extra objects in the JSON line:
   parity        key points, descriptors and matches12 of one camera slot per DISTINCT scene (64) of the LAST timed step compared bit for bit with the
@@ -114,7 +117,7 @@ def cpu_baseline(frames, budget_s=8.0, blur_round_mode=0):
     tsteps, batch = frames.shape[0], frames.shape[1]
     slots = [[np.ascontiguousarray(frames[t, b, :, :W]) for t in range(tsteps)] for b in range(min(batch, 16))]
     ncores = os.cpu_count() or 1
-    ctx = mp.get_context("fork")
+    ctx = mp.get_context("spawn")                               # this process holds the GPU: fresh workers, not forked copies of it
     with ctx.Pool(1) as pool:                                   # the single-thread rate in a child too: the library choice is per process
         one_done, one_dt = pool.map(_cpu_worker, [(slots[0], min(budget_s, 6.0), kind, blur_round_mode)])[0]
         port_done, port_dt = pool.map(_cpu_worker, [(slots[0], 3.0, "port", blur_round_mode)])[0] if kind == "reference" else (one_done, one_dt)
@@ -380,6 +383,40 @@ def parity_of_last_step(host_frames, kps, descs, m12, last_step, T, blur_round_m
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, kps, descs, m12, nm, cap):
+    """`--dump-outputs DIR`: the arrays the last timed step handed its caller, for `nslots` camera slots (all of them when they fit in
+    DUMP_LIMIT_BYTES at full key point capacity, else a sample drawn with a fixed seed), written as DIR/<name>.npy:
+      slots [S]                        the camera slots dumped, ascending
+      keypoints [sum n, 7] f8          x, y, size, angle, response, octave, class_id of every key point of those slots, slot after slot
+      keypoints_per_slot [S] f8        n per slot
+      descriptors [sum n, 32] f4       the 32 descriptor bytes of every key point
+      matches12 [sum n1, ] f8          SearchForInitialization: per key point of the slot's previous frame, the matched key point or -1
+      matches12_per_slot [S] f8        n1 per slot
+      matches_per_slot [S] f8          matches found per slot
+    (the matches12 files are absent with --extract-only).  Returns a summary for the JSON line."""
+    B = len(kps)
+    per_slot = cap * (7 * 8 + 32 * 4 + 8) + 4 * 8                          # worst case: every slot at full capacity
+    nslots = min(B, max(1, (DUMP_LIMIT_BYTES - 4096) // per_slot))
+    slots = np.arange(B) if nslots == B else np.sort(np.random.default_rng(0).choice(B, nslots, replace=False))
+    arrays = {"slots": slots.astype(np.float64),
+              "keypoints": np.concatenate([np.stack([kps[b][f].astype(np.float64) for f in kps[b].dtype.names], axis=1) for b in slots]).reshape(-1, 7),
+              "keypoints_per_slot": np.array([len(kps[b]) for b in slots], np.float64),
+              "descriptors": np.concatenate([descs[b] for b in slots]).reshape(-1, 32).astype(np.float32)}
+    if m12[0] is not None:
+        arrays["matches12"] = np.concatenate([m12[b] for b in slots]).astype(np.float64)
+        arrays["matches12_per_slot"] = np.array([len(m12[b]) for b in slots], np.float64)
+        arrays["matches_per_slot"] = nm[slots].astype(np.float64)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_LIMIT_BYTES, nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "slots": int(nslots), "of_slots": B, "files": sorted(arrays), "bytes": int(nbytes)}
+
+
 def pool_mode(args):
     """`--pool`: the product-side multi-GPU owner (orbhip_pool_*, what north_star describes: ONE process, one host thread + context +
     pinned staging ring per GPU, camera c on devices[c mod G], no collective) timed at the drop-in boundary — host frames in, host key
@@ -511,9 +548,11 @@ def multi_gpu_extras(args, G, share):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=150)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 150; 20 with --pool)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="measurements of --steps steps each; value = the median one")
+    ap.add_argument("--repeats", type=int, default=1, help="measurements of --steps steps each; value = the median one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (a fixed sample of camera slots, at most 64 MB) "
+                    "as DIR/<name>.npy in float32 / float64; rank 0")
     ap.add_argument("--no-host-io", action="store_true", help="skip the PCIe-inclusive host-buffer measurement (host_io object)")
     ap.add_argument("--batch", type=int, default=512, help="camera slots (frames) per step per GPU")
     ap.add_argument("--tsteps", type=int, default=4, help="distinct resident time steps cycled through")
@@ -537,6 +576,10 @@ def main():
     ap.add_argument("--extras-db-keyframes", type=int, default=10000, help="key frames (x 2000 descriptors) of the sharded database of config5_sharded")
     ap.add_argument("--extract-only", action="store_true", help="diagnostic: skip the matcher (NOT the metric's workload; the JSON line says so)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 20 if args.pool else 150
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.host_io_only:
         from orb_slam2_amd import synth
         frames = np.zeros((1, 256, H, W), np.uint8)
@@ -547,8 +590,6 @@ def main():
         print(json.dumps(host_io(None, frames, args.device, args.blur_round_mode)), flush=True)
         return
     if args.pool:
-        if args.steps == 150:
-            args.steps = 20
         return pool_mode(args)
 
     # No framework in this process, at any N: the library runs on the HIP runtime its RUNPATH names (/opt/rocm — the one the tests, smoke()
@@ -628,6 +669,7 @@ def main():
     kps, descs = ex.fetch(B)
     m12, nm = ([None] * B, np.zeros(B, np.int32)) if args.extract_only else ex.fetch_matches(B)
     nkp = [len(k) for k in kps]
+    dumped = dump_outputs(args.dump_outputs, kps, descs, m12, nm, ex.capacity) if rank == 0 and args.dump_outputs else None
     parity = parity_of_last_step(host_frames, kps, descs, m12, last_step, T, args.blur_round_mode, args.parity_slots) if rank == 0 and args.parity_slots > 0 else None
 
     alg_bytes_per_frame = ex.algorithmic_bytes_per_frame()
@@ -705,6 +747,7 @@ def main():
             "kernel_time_fraction_of_step": round(total_kernel_ms / (elapsed / args.steps * 1e3), 3),
             "check": {"keypoints_per_frame_min_max": [int(min(nkp)), int(max(nkp))], "matches_per_frame_min_max": [int(nm.min()), int(nm.max())]},
             "parity": parity,
+            "dump_outputs": dumped,
             "runtime": {"library": runtime_line, "mapped": orb_slam2_amd.mapped_hip_runtimes(), "framework_imported": "torch" in sys.modules, "control_plane": control},
         }
         closed = world > 1 and not args.no_extras

@@ -33,7 +33,8 @@ def _locked_make(args):
     import tempfile
     if os.environ.get("ORBHIP_NO_MAKE"):      # sanitizer runs (tools/sanitize_concurrency.sh builds everything first): fork() under a preloaded ThreadSanitizer runtime can deadlock
         return
-    with open(os.path.join(tempfile.gettempdir(), "orbhip_test_make.lock"), "w") as lk:
+    # per user: a lock file another user left in a shared temporary directory cannot be opened for writing
+    with open(os.path.join(tempfile.gettempdir(), f"orbhip_test_make_{os.getuid()}.lock"), "w") as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         try:
             subprocess.check_call(["make"] + list(args))

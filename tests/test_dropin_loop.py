@@ -53,22 +53,16 @@ def run_and_compare(S, D, cfg, nframes, seed, kf_every):
     return ref, got
 
 
-def test_front_end_loop_small(builds, request):
-    if "gpu" in request.node.name:
-        pytest.skip("the GPU runs use the BASELINE shapes")
+def test_front_end_loop_small(builds):
     S, D = builds
     run_and_compare(S, D, SMALL, nframes=7, seed=3, kf_every=3)
 
 
-@pytest.mark.gpu
 @pytest.mark.parametrize("name,cfg", [("euroc", EUROC), ("kitti", KITTI)])
 def test_front_end_loop_baseline_shapes(builds, request, name, cfg):
-    """>= 20 stereo frames at 752x480 / 1200 and 1241x376 / 2000, on the MI355X, through the reference's Frame.cc / ORBmatcher.cc"""
-    if "gpu" not in request.node.name.split("[")[1]:
-        pytest.skip("full shapes run on the GPU builds")
+    """>= 20 stereo frames at 752x480 / 1200 and 1241x376 / 2000 through the reference's Frame.cc / ORBmatcher.cc: on the MI355X with the "-gpu"
+    builds (marked gpu by the fixture), on the CPU emulation of the same kernels with the others"""
     S, D = builds
-    if "steps1-3" in request.node.name and name == "kitti":
-        pytest.skip("one shape is enough for the steps 1-3 build")
     ref, got = run_and_compare(S, D, cfg, nframes=24, seed=5, kf_every=5)
     ms_ref, ms_got = np.median([f.ms for f in ref[1:]]), np.median([f.ms for f in got[1:]])
     part = lambda fs: " + ".join(f"{np.median([getattr(f, k) for f in fs[1:]]):.3f}" for k in ("ms_ctor", "ms_motion", "ms_local"))

@@ -129,12 +129,11 @@ def test_pool_cameras_round_robin(backend, frames, want, monkeypatch):
     pool.close()
 
 
+@pytest.mark.parametrize("backend", ["emu"], indirect=True)          # the fault-injection hook is compiled into the CPU emulation build only (-DORBHIP_TEST_HOOKS)
 def test_pool_survives_partial_submit_failure(backend, frames, want, monkeypatch):
     """One device refuses a round (injected): the round keeps its ticket (the other device's part must be collected in order), collect
     delivers the healthy cameras and reports the refusal, and the pool keeps working — a context ticket nobody collects would wedge its
     ring for good.  A round NO device takes fails at submit, without a ticket."""
-    if not backend.endswith("_emu.so"):
-        pytest.skip("the fault-injection hook is compiled into the CPU emulation build only (-DORBHIP_TEST_HOOKS), not into liborbhip.so")
     devices = _pool_devices(backend, monkeypatch, 2)
     pool = orb_slam2_amd.MultiGpuExtractor(devices, 4, N, 1.2, 8, 20, 7, W, H, library=backend)
     t0 = pool.submit(frames[:4])

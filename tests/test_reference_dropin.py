@@ -47,8 +47,6 @@ def _same(a, b):
 @pytest.mark.parametrize("w,h,n,levels,scale,blur", [(480, 360, 700, 8, 1.2, 0), (333, 250, 300, 6, 1.3, 0), (480, 360, 700, 8, 1.2, 1)])
 def test_reference_frame_on_dropin_extractor(builds, request, monkeypatch, w, h, n, levels, scale, blur):
     S, D = builds
-    if "all-steps" in request.node.name and (w != 480 or blur):
-        pytest.skip("one geometry is enough for the forwarding members")
     # blur = 1: the rounding of cv::GaussianBlur in an x86-64 (SSE2) OpenCV build — the drop-in class's own default on such hosts — on both sides
     monkeypatch.setenv("ORB_REF_BLUR_ROUND_MODE", str(blur))
     seq = synth.sequence(w, h, 2, seed=w + n)
@@ -102,12 +100,11 @@ def test_reference_stereo_frame_on_dropin_extractors(builds):
     S.RefFrame._geometry = None
 
 
-def test_projection_matchers_through_the_binding(builds, request):
+def test_projection_matchers_through_the_binding(builds):
     """INTEGRATION.md §2-3c in the "all-steps" build: ORBmatcher::SearchByProjection(Frame, MapPoints, th) and (CurrentFrame, LastFrame, th, bMono)
     keep the reference's projection / bookkeeping code and send their search loops through orbhip_search_by_projection_bounds; the final
-    Frame::mvpMapPoints and the return values must equal the unmodified reference's, on mono and stereo frames."""
-    if "all-steps" not in request.node.name:
-        pytest.skip("the steps 1-3 build keeps the reference's own search loops")
+    Frame::mvpMapPoints and the return values must equal the unmodified reference's, on mono and stereo frames.  The "steps1-3" build keeps the
+    reference's own search loops: there the same comparison checks them on the drop-in extractor's frames."""
     S, D = builds
     w, h, n = 480, 360, 700
     seq = synth.sequence(w, h, 2, seed=41)
@@ -148,14 +145,13 @@ def test_projection_matchers_through_the_binding(builds, request):
     S.RefFrame._geometry = None
 
 
-def test_back_end_matchers_through_the_binding(builds, request):
+def test_back_end_matchers_through_the_binding(builds):
     """The other two SearchByProjection overloads (loop closing: KeyFrame + Sim3, ORBmatcher.cc:290-403; relocalisation: Frame + KeyFrame,
     :1472-1599) with their search loops sent through orbhip_search_by_projection_bounds, and ORBmatcher::Fuse(pKF, vpMapPoints, th) (:825-972)
     around orbhip_search_best_in_window_bounds, both SearchByBoW overloads (:159-288, :522-655) through orbhip_search_by_bow and
     SearchForTriangulation (:657-823) through orbhip_search_for_triangulation, SearchBySim3 (:1102-1326) through two
-    orbhip_search_best_in_window_bounds calls, in the "all-steps" build."""
-    if "all-steps" not in request.node.name:
-        pytest.skip("the steps 1-3 build keeps the reference's own search loops")
+    orbhip_search_best_in_window_bounds calls, in the "all-steps" build; in the "steps1-3" build the same comparison checks the reference's own loops on
+    the drop-in extractor's frames."""
     import os, sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from test_reference_matchers import _world

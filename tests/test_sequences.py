@@ -66,19 +66,15 @@ def _voc(tmp_path_factory):
 
 
 @pytest.mark.parametrize("sensor", ["mono", "rgbd"])
-def test_sequences_small(builds, request, tmp_path_factory, sensor):
-    if "gpu" in request.node.name:
-        pytest.skip("the GPU runs use configs[0]'s shape")
+def test_sequences_small(builds, tmp_path_factory, sensor):
     S, D = builds
     run_and_compare(S, D, sensor, SMALL, nframes=12, voc_path=_voc(tmp_path_factory), dist=TUM1_DIST if sensor == "rgbd" else None)
 
 
-@pytest.mark.gpu
 @pytest.mark.parametrize("sensor", ["mono", "rgbd"])
 def test_sequences_tum_shape(builds, request, tmp_path_factory, sensor):
-    """BASELINE.json configs[0]'s shape (TUM fr1: 640x480, 1000 features, TUM1.yaml's camera - its distortion for the RGB-D run), 24 frames on the MI355X"""
-    if "gpu" not in request.node.name.split("[")[1]:
-        pytest.skip("full shapes run on the GPU builds")
+    """BASELINE.json configs[0]'s shape (TUM fr1: 640x480, 1000 features, TUM1.yaml's camera - its distortion for the RGB-D run), 24 frames: on the
+    MI355X with the "-gpu" builds (marked gpu by the fixture), on the CPU emulation of the same kernels with the others"""
     S, D = builds
     ref, got = run_and_compare(S, D, sensor, TUM1, nframes=24, voc_path=_voc(tmp_path_factory), dist=TUM1_DIST if sensor == "rgbd" else None, kf_every=4)
     ms_ref, ms_got = np.median([f.ms for f in ref[2:]]), np.median([f.ms for f in got[2:]])

@@ -313,7 +313,7 @@ def config4(w, h, n, ncam, ncores, rounds=12, cpu_budget_s=5.0, fast=True):
     from oracle import orb_oracle as O
     frames = [synth.frame(w, h, seed=700 + c) for c in range(ncam)]
     nw = ncores
-    ctx = mp.get_context("fork")
+    ctx = mp.get_context("spawn")                                # config5 has touched the device in this process by now: fresh workers, not forked ones
     with ctx.Pool(nw) as pool:                                   # before this process creates its pool of device contexts
         res = pool.map(_rig_cpu_worker, [([frames[i % ncam]], cpu_budget_s, n, fast) for i in range(nw)])
     cpu_rate = sum(r[0] / r[1] for r in res)
