@@ -224,6 +224,17 @@ hipError_t arena_download(hipStream_t s)
     for (const Xfer& x : g_xfers) if (x.dst) memcpy(x.dst, g_hstage + x.off, x.bytes_out);
     return hipSuccess;
 }
+// One matcher call on the calling thread's arena: lay it out (above floor, see arena_layout), upload its inputs, launch, download its answers.
+// After a failure the stream is synchronised: never leave a copy in flight on the per-thread mirrors.
+template <typename Layout, typename Launch> static hipError_t arena_call(int device, hipStream_t s, Layout layout, Launch launch, size_t floor = 0)
+{
+    hipError_t e = arena_layout(device, layout, floor);
+    if (e == hipSuccess) e = arena_upload(s);
+    if (e == hipSuccess) { launch(); e = hipGetLastError(); }
+    if (e == hipSuccess) e = arena_download(s);
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+}
 hipError_t orbhip_arena_reserve(int device, size_t bytes)
 {
     if (g_scratch_dev != device || g_scratch_bytes < bytes) {
@@ -348,6 +359,7 @@ extern "C" const char* orbhip_version(void) { return "orbhip 0.2 (gfx950)"; }
 thread_local double orbhip_tl_api_ms = 0; thread_local int orbhip_tl_api_depth = 0;
 extern "C" double orbhip_thread_api_ms(int reset) { const double v = orbhip_tl_api_ms; if (reset) orbhip_tl_api_ms = 0; return v; }
 extern "C" int orbhip_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; } return n; }
+static bool device_present() { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n >= 1; }
 extern "C" const char* orbhip_last_error(void) { return g_err.c_str(); }
 
 extern "C" void orbhip_destroy(orbhip_ctx* c)
@@ -1131,16 +1143,21 @@ static int host_chunk_frames(int nimg, bool dma_both_ways)
 
 static int stereo_row_cap(const orbhip_ctx* c) { return c->out_cap * ((int)ceilf(4.0f * c->sf[c->L - 1]) + 3); }      // rows [floor(y-r), ceil(y+r)], r = 2*scale
 static StereoSide stereo_side(orbhip_ctx* c);
+// Frame::AssignFeaturesToGrid over ALL key points of nslots frames kp[slot][cap] (counts d_n[slot]) into the tables at [slot]: k_match_grid with grid_all_levels
+static void launch_feature_grid(const orbhip_keypoint* kp, const int* d_n, int cap, const orbhip_bounds& b, int* grid_start, int* grid_items, float2* grid_xy,
+                                int nslots, int slot0, hipStream_t s)
+{
+    MatchParams M; memset(&M, 0, sizeof M);
+    M.kp2 = kp; M.n2 = d_n; M.cap = cap; M.min_x = b.min_x; M.min_y = b.min_y; M.max_x = b.max_x; M.max_y = b.max_y;
+    M.grid_start = grid_start; M.grid_items = grid_items; M.grid_xy = grid_xy; M.grid_all_levels = 1; M.slot0 = slot0;
+    orbhip_launch_match_grid(M, nslots, s);
+}
 // what the follow-up calls of a single-image extraction will ask for, enqueued behind its result download (see orbhip_ctx::want_fgrid)
 static orbhip_status frame_epilogues(orbhip_ctx* c, hipStream_t s)
 {
     if (c->want_fgrid) {
         if (!c->d_fgrid_start) { HIPCHK(dalloc(&c->d_fgrid_start, (size_t)ORBHIP_GRID_CELLS + 1)); HIPCHK(dalloc(&c->d_fgrid_items, (size_t)c->out_cap)); HIPCHK(dalloc(&c->d_fgrid_xy, (size_t)c->out_cap)); }
-        MatchParams M; memset(&M, 0, sizeof M);
-        M.kp2 = (c->distorted ? c->d_out_kpun : c->d_out_kp)[c->cur]; M.n2 = c->d_out_n[c->cur]; M.cap = c->out_cap;
-        M.min_x = c->bounds.min_x; M.min_y = c->bounds.min_y; M.max_x = c->bounds.max_x; M.max_y = c->bounds.max_y;
-        M.grid_start = c->d_fgrid_start; M.grid_items = c->d_fgrid_items; M.grid_xy = c->d_fgrid_xy; M.grid_all_levels = 1;
-        orbhip_launch_match_grid(M, 1, s);
+        launch_feature_grid((c->distorted ? c->d_out_kpun : c->d_out_kp)[c->cur], c->d_out_n[c->cur], c->out_cap, c->bounds, c->d_fgrid_start, c->d_fgrid_items, c->d_fgrid_xy, 1, 0, s);
         c->fgrid_valid = true; c->fgrid_cur = c->cur;
     }
     if (c->want_rrows) {
@@ -1468,82 +1485,121 @@ static bool projection_ok(const orbhip_projection* P)
 {
     return P && P->kind >= ORBHIP_PROJ_LAST_FRAME && P->kind <= ORBHIP_PROJ_SIM3 && P->gemm_mode >= 0 && P->gemm_mode <= 2 && P->nlevels >= 1 && P->nlevels <= ORBHIP_MAX_PROJ_LEVELS;
 }
-static void gated_out(orbhip_proj_query* q, int np) { if (q) for (int i = 0; i < np; i++) { memset(&q[i], 0, sizeof q[i]); q[i].radius = -1.0f; } }
-static void gated_out(orbhip_best_query* q, int np) { if (q) for (int i = 0; i < np; i++) { memset(&q[i], 0, sizeof q[i]); q[i].radius = -1.0f; } }
+template <typename Query> static void gated_out(Query* q, int np) { if (q) for (int i = 0; i < np; i++) { memset(&q[i], 0, sizeof q[i]); q[i].radius = -1.0f; } }
+static void no_match(int32_t* best_idx, int32_t* best_dist, int nq) { for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; } }
+// a host input the kernels only read: laid out like Arena::io, its device copy handed back as a pointer to const
+template <typename T> static void arena_in(Arena& A, const T** p, const T* src, size_t count) { T* d = nullptr; A.io(&d, count, src, count); *p = d; }
 
-// queries given (P == nullptr) or derived on the device from map points under *P (orbhip_project_search_bounds): `queries` is then nullptr and nq = the point count
-static orbhip_status search_by_projection_impl(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right,
-                                               const uint8_t* blocked, int n, const orbhip_bounds* bounds,
-                                               const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
-                                               const orbhip_projection* P, const orbhip_map_point* points, orbhip_proj_query* queries_out,
-                                               int mode, float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches)
+// The frame a single-frame search looks in: host arrays that travel in the call's arena (host_frame), or a frame of a context's last extraction
+// that is still on the device (frame_args), of which only the queries travel.
+struct SearchFrame {
+    int device; hipStream_t stream;             // a context's stream; host arrays use the calling thread's, taken once the device is set
+    int n; orbhip_bounds bounds; bool on_host;
+    const orbhip_keypoint* kps; const uint8_t* desc; const float* u_right;      // host or device pointers (u_right may be nullptr)
+    const int* grid_start = nullptr; const int* grid_items = nullptr; const float2* grid_xy = nullptr;      // the frame's grid, already on the device; nullptr: the search builds it
+    bool* want_grid = nullptr;                  // set when the search runs: the context then builds the grid behind each single-image extraction
+};
+static orbhip_status host_frame(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right, int n, const orbhip_bounds* bounds, SearchFrame* F)
+{
+    if (n < 0 || (n > 0 && (!kps || !desc)) || !bounds || !(bounds->max_x > bounds->min_x) || !(bounds->max_y > bounds->min_y)) return fail(ORBHIP_ERR_INVALID, "bad argument");
+    *F = SearchFrame{device, nullptr, n, *bounds, true, kps, desc, u_right};
+    return ORBHIP_OK;
+}
+// key points (mvKeysUn with a distorted camera attached), descriptors and - if asked for - mvuRight of the last stereo / RGB-D step are read where the extraction left them
+static orbhip_status frame_args(orbhip_ctx* c, int frame, int n, int use_u_right, SearchFrame* F)
+{
+    if (!c) return fail(ORBHIP_ERR_INVALID, "null context");
+    if (frame < 0 || frame >= c->last_nimg) return fail(ORBHIP_ERR_INVALID, "frame %d outside the %d frames of the last extraction", frame, c->last_nimg);
+    if (n < 0 || n > c->out_cap) return fail(ORBHIP_ERR_INVALID, "n %d outside 0..%d", n, c->out_cap);
+    if (use_u_right && !c->d_last_uright) return fail(ORBHIP_ERR_INVALID, "no mvuRight on the device: run orbhip_compute_stereo_matches / orbhip_compute_stereo_from_rgbd on this context first");
+    *F = SearchFrame{c->cfg.device, c->stream, n, c->bounds, false, (c->distorted ? c->d_out_kpun : c->d_out_kp)[c->cur] + (size_t)frame * c->out_cap,
+                     c->d_out_desc[c->cur] + (size_t)frame * c->out_cap * 32, use_u_right ? c->d_last_uright + (size_t)frame * c->out_cap : nullptr};
+    // the grid of this frame was built behind its extraction (frame epilogue, same stream): take it; from now on it always will be
+    if (frame == 0 && c->fgrid_valid && c->fgrid_cur == c->cur && c->last_n_valid && c->last_n[0] == n) { F->grid_start = c->d_fgrid_start; F->grid_items = c->d_fgrid_items; F->grid_xy = c->d_fgrid_xy; }
+    if (c->last_nimg == 1 || c->pair_mode) F->want_grid = &c->want_fgrid;
+    return ORBHIP_OK;
+}
+
+// queries given (P == nullptr) or derived on the device from map points under *P (orbhip_project_search_*): `queries` is then nullptr and nq = the point count
+static orbhip_status search_by_projection(const SearchFrame& F, const uint8_t* blocked, const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
+                                          const orbhip_projection* P, const orbhip_map_point* points, orbhip_proj_query* queries_out,
+                                          int mode, float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches)
 {
     OrbApiTimer api_timer;
-    if (n < 0 || nq < 0 || !nmatches || (n > 0 && (!kps || !desc || !feature_query)) || (nq > 0 && ((!queries && !points) || !query_desc)) || !bounds || !(bounds->max_x > bounds->min_x) || !(bounds->max_y > bounds->min_y) || (mode != 0 && mode != 1) ||
-        (points && !projection_ok(P)))
+    const int n = F.n;
+    if (nq < 0 || !nmatches || (n > 0 && !feature_query) || (nq > 0 && ((!queries && !points) || !query_desc)) || (mode != 0 && mode != 1) || (points && !projection_ok(P)))
         return fail(ORBHIP_ERR_INVALID, "bad argument");
     *nmatches = 0;
     for (int i = 0; i < n; i++) feature_query[i] = -1;
     if (points) gated_out(queries_out, nq);
     if (n == 0 || nq == 0) return ORBHIP_OK;
-    if (n >= (1 << 19)) return fail(ORBHIP_ERR_UNSUPPORTED, "too many features");
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    orbhip_keypoint* dk = nullptr; uint8_t *dd = nullptr, *dqd = nullptr; unsigned char *dbl_in = nullptr; float* dur = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dfq = nullptr, *dev = nullptr, *dbig = nullptr;
+    if (F.on_host && n >= (1 << 19)) return fail(ORBHIP_ERR_UNSUPPORTED, "too many features");
+    if (F.on_host && !device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    HIPCHK(hipSetDevice(F.device));
+    const hipStream_t s = F.on_host ? orbhip_thread_stream(F.device) : F.stream;
+    const orbhip_keypoint* dk = F.kps; const uint8_t* dd = F.desc; const float* dur = F.u_right;      // (host arrays: replaced by their copies)
+    uint8_t* dqd = nullptr; unsigned char* dbl_in = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dfq = nullptr, *dev = nullptr, *dbig = nullptr;
     float2* dgxy = nullptr; orbhip_proj_query* dq = nullptr; unsigned* dcand = nullptr; unsigned* dtop = nullptr;
     orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
     const int hn[2] = {n, 0}; int hres[2] = {0, 0};
-    TRY(arena_layout(device, [&](Arena& A) {
-        A.io(&dk, n, kps, n); A.io(&dd, (size_t)n * 32, desc, (size_t)n * 32); A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32);
+    const hipError_t e = arena_call(F.device, s, [&](Arena& A) {
+        if (F.on_host) { arena_in(A, &dk, F.kps, n); arena_in(A, &dd, F.desc, (size_t)n * 32); }
+        A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32);
         if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, P, 1); A.io(&dq, nq, (const orbhip_proj_query*)nullptr, 0, queries_out, queries_out ? nq : 0); }
         else A.io(&dq, nq, queries, nq);
-        if (u_right) A.io(&dur, n, u_right, n);
+        if (F.on_host && F.u_right) arena_in(A, &dur, F.u_right, n);
         if (blocked) A.io(&dbl_in, n, blocked, n);
         A.io(&dn, 8, hn, 2, hres, 2);                         // [0] = n in, [1] = the return value out
         A.io(&dfq, n, (const int*)nullptr, 0, feature_query, n);
         A.take(&dgs, ORBHIP_GRID_CELLS + 1); A.take(&dgi, n); A.take(&dgxy, n); A.take(&dnc, nq); A.take(&dev, nq);
         A.take(&dcand, (size_t)nq * n); A.take(&dtop, (size_t)nq * 5);
         if (orbhip_proj_select_big(n)) A.take(&dbig, (size_t)4 * n);      // the select kernel's per-feature tables when they do not fit LDS
-    }));
-    TRY(arena_upload(ts));
-    if (e == hipSuccess) {
-        MatchParams M; memset(&M, 0, sizeof M);
-        M.kp2 = dk; M.n2 = dn; M.cap = n; M.min_x = bounds->min_x; M.min_y = bounds->min_y; M.max_x = bounds->max_x; M.max_y = bounds->max_y; M.grid_start = dgs; M.grid_items = dgi; M.grid_xy = dgxy; M.grid_all_levels = 1;
-        orbhip_launch_match_grid(M, 1, ts);
+    }, [&] {
+        const int* gs = F.grid_start; const int* gi = F.grid_items; const float2* gxy = F.grid_xy;
+        if (!gs) { launch_feature_grid(dk, dn, n, F.bounds, dgs, dgi, dgxy, 1, 0, s); gs = dgs; gi = dgi; gxy = dgxy; }
+        if (F.want_grid) *F.want_grid = true;
         ProjParams J; memset(&J, 0, sizeof J);
-        J.kp = dk; J.desc = dd; J.u_right = dur; J.n = n; J.min_x = bounds->min_x; J.min_y = bounds->min_y; J.max_x = bounds->max_x; J.max_y = bounds->max_y; J.grid_start = dgs; J.grid_items = dgi; J.grid_xy = dgxy;
+        J.kp = dk; J.desc = dd; J.u_right = dur; J.n = n; J.min_x = F.bounds.min_x; J.min_y = F.bounds.min_y; J.max_x = F.bounds.max_x; J.max_y = F.bounds.max_y; J.grid_start = gs; J.grid_items = gi; J.grid_xy = gxy;
         J.q = dq; J.qdesc = dqd; J.nq = nq; J.cand = dcand; J.ncand = dnc; J.cand_stride = n; J.top = dtop;
         J.pts = dpts; J.proj = dP; J.q_out = dq;
         J.blocked_in = dbl_in; J.blocked_out = nullptr; J.feature_query = dfq; J.nmatches = dn + 1; J.events = dev;
         J.mode = mode; J.nnratio = nnratio; J.th_high = th_high; J.check_ori = check_ori; J.big_ws = dbig;
-        orbhip_launch_proj(J, ts);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(ts));
-    if (e != hipSuccess) (void)hipStreamSynchronize(ts);            // never leave a copy in flight on the per-thread mirrors
-    if (e == hipSuccess) *nmatches = hres[1];
-#undef TRY
-    orbhip_status st = ORBHIP_OK;
-    if (e != hipSuccess) st = fail(ORBHIP_ERR_HIP, "search_by_projection: %s", hipGetErrorString(e));
-    return st;
+        orbhip_launch_proj(J, s);
+    });
+    if (e != hipSuccess) return fail(ORBHIP_ERR_HIP, F.on_host ? "search_by_projection: %s" : "search_by_projection_frame: %s", hipGetErrorString(e));
+    *nmatches = hres[1];
+    return ORBHIP_OK;
 }
 extern "C" orbhip_status orbhip_search_by_projection_bounds(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right,
                                                      const uint8_t* blocked, int n, const orbhip_bounds* bounds,
                                                      const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
                                                      int mode, float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches)
 {
-    if (nq > 0 && !queries) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    return search_by_projection_impl(device, kps, desc, u_right, blocked, n, bounds, queries, query_desc, nq, nullptr, nullptr, nullptr, mode, nnratio, th_high, check_ori, feature_query, nmatches);
+    SearchFrame F; const orbhip_status st = host_frame(device, kps, desc, u_right, n, bounds, &F); if (st != ORBHIP_OK) return st;
+    return search_by_projection(F, blocked, queries, query_desc, nq, nullptr, nullptr, nullptr, mode, nnratio, th_high, check_ori, feature_query, nmatches);
 }
 extern "C" orbhip_status orbhip_project_search_bounds(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right, const uint8_t* blocked, int n, const orbhip_bounds* bounds,
                                                       const orbhip_projection* proj, const orbhip_map_point* points, const uint8_t* point_desc, int np,
                                                       float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches, orbhip_proj_query* queries_out)
 {
+    SearchFrame F; const orbhip_status st = host_frame(device, kps, desc, u_right, n, bounds, &F); if (st != ORBHIP_OK) return st;
+    return search_by_projection(F, blocked, nullptr, point_desc, np, np > 0 ? proj : nullptr, np > 0 ? points : nullptr, queries_out, 1, nnratio, th_high, check_ori, feature_query, nmatches);
+}
+extern "C" orbhip_status orbhip_search_by_projection_frame(orbhip_ctx* c, int frame, int n, int use_u_right, const uint8_t* blocked,
+                                                           const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
+                                                           int mode, float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches)
+{
+    if (nq > 0 && !queries) return fail(ORBHIP_ERR_INVALID, "bad argument");
+    SearchFrame F; const orbhip_status st = frame_args(c, frame, n, use_u_right, &F); if (st != ORBHIP_OK) return st;
+    return search_by_projection(F, blocked, queries, query_desc, nq, nullptr, nullptr, nullptr, mode, nnratio, th_high, check_ori, feature_query, nmatches);
+}
+extern "C" orbhip_status orbhip_project_search_frame(orbhip_ctx* c, int frame, int n, int use_u_right, const uint8_t* blocked,
+                                                     const orbhip_projection* proj, const orbhip_map_point* points, const uint8_t* point_desc, int np,
+                                                     float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches, orbhip_proj_query* queries_out)
+{
     if (np > 0 && (!points || !proj)) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    return search_by_projection_impl(device, kps, desc, u_right, blocked, n, bounds, nullptr, point_desc, np, np > 0 ? proj : nullptr, np > 0 ? points : nullptr, queries_out, 1, nnratio, th_high, check_ori, feature_query, nmatches);
+    SearchFrame F; const orbhip_status st = frame_args(c, frame, n, use_u_right, &F); if (st != ORBHIP_OK) return st;
+    return search_by_projection(F, blocked, nullptr, point_desc, np, np > 0 ? proj : nullptr, np > 0 ? points : nullptr, queries_out, 1, nnratio, th_high, check_ori, feature_query, nmatches);
 }
 
 // Several frames in one pass: every per-slot array lives at [slot][cap] of one arena (one copy each way), the order-dependent kernel runs
@@ -1566,38 +1622,32 @@ extern "C" orbhip_status orbhip_search_by_projection_batch(int device, int nslot
     if (!work) return ORBHIP_OK;
     if (cap >= (1 << 19)) return fail(ORBHIP_ERR_UNSUPPORTED, "too many features");
     if ((size_t)nslots * qcap * cap * sizeof(unsigned) > ((size_t)2 << 30)) return fail(ORBHIP_ERR_UNSUPPORTED, "candidate lists of %d slots x %d queries x %d features exceed 2 GB: split the batch", nslots, qcap, cap);
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    if (!device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
     HIPCHK(hipSetDevice(device));
     hipStream_t ts = orbhip_thread_stream(device);
-    orbhip_keypoint* dk = nullptr; uint8_t *dd = nullptr, *dqd = nullptr; unsigned char* dbl = nullptr; float* dur = nullptr; int *dn = nullptr, *dnm = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dfq = nullptr, *dev = nullptr, *dbig = nullptr;
-    float2* dgxy = nullptr; orbhip_proj_query* dq = nullptr; unsigned *dcand = nullptr, *dtop = nullptr; ProjParams* dJ = nullptr;
+    int *dn = nullptr, *dnm = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dev = nullptr, *dbig = nullptr; float2* dgxy = nullptr; unsigned *dcand = nullptr, *dtop = nullptr; ProjParams* dJ = nullptr;
     std::vector<int> hn(nslots), hnm(nslots, 0); std::vector<ProjParams> hJ(nslots);
     std::vector<float> no_ur(any_ur ? cap : 0, -1.0f); std::vector<uint8_t> no_bl(any_bl ? cap : 0, 0);
     for (int s = 0; s < nslots; s++) hn[s] = slots[s].n;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
     const size_t C = (size_t)cap, Q = (size_t)qcap;
-    {   // the parameter table is read from hJ when the arena is uploaded, i.e. after the device addresses below have been filled in
-        TRY(arena_layout(device, [&](Arena& A) {
-            A.io(&dJ, (size_t)nslots, (const ProjParams*)hJ.data(), (size_t)nslots);
-            A.io(&dn, (size_t)nslots, (const int*)hn.data(), (size_t)nslots);
-            A.io(&dnm, (size_t)nslots, (const int*)hnm.data(), (size_t)nslots, hnm.data(), (size_t)nslots);
-            for (int s = 0; s < nslots; s++) {                                        // [slot][cap] / [slot][qcap] blocks, each slot's rows from its own host arrays
-                const orbhip_proj_slot& S = slots[s];
-                orbhip_keypoint* k = nullptr; uint8_t *d = nullptr, *qd = nullptr; orbhip_proj_query* q = nullptr; float* ur = nullptr; unsigned char* bl = nullptr; int* fq = nullptr;
-                A.io(&k, C, S.kps, (size_t)S.n); A.io(&d, C * 32, S.desc, (size_t)S.n * 32); A.io(&q, Q, S.queries, (size_t)S.nq); A.io(&qd, Q * 32, S.query_desc, (size_t)S.nq * 32);
-                if (any_ur) A.io(&ur, C, S.u_right ? S.u_right : no_ur.data(), (size_t)S.n);
-                if (any_bl) A.io(&bl, C, (const unsigned char*)(S.blocked ? S.blocked : no_bl.data()), (size_t)S.n);
-                A.io(&fq, C, (const int*)nullptr, 0, S.feature_query, (size_t)S.n);
-                if (s == 0) { dk = k; dd = d; dq = q; dqd = qd; dur = ur; dbl = bl; dfq = fq; }
-                ProjParams& J = hJ[s]; memset(&J, 0, sizeof J);
-                J.kp = k; J.desc = d; J.u_right = S.u_right ? ur : nullptr; J.n = S.n; J.q = q; J.qdesc = qd; J.nq = S.nq; J.blocked_in = S.blocked ? bl : nullptr; J.feature_query = fq;
-            }
-            A.take(&dgs, (size_t)nslots * (ORBHIP_GRID_CELLS + 1)); A.take(&dgi, nslots * C); A.take(&dgxy, nslots * C); A.take(&dnc, nslots * Q); A.take(&dev, nslots * Q);
-            A.take(&dcand, nslots * Q * C); A.take(&dtop, nslots * Q * 5);
-            if (orbhip_proj_select_big(cap)) A.take(&dbig, nslots * 4 * C);      // the select kernel's per-feature tables when the largest slot's do not fit LDS
-        }));
-        for (int s = 0; s < nslots && e == hipSuccess; s++) {
+    const hipError_t e = arena_call(device, ts, [&](Arena& A) {
+        A.io(&dJ, (size_t)nslots, (const ProjParams*)hJ.data(), (size_t)nslots);
+        A.io(&dn, (size_t)nslots, (const int*)hn.data(), (size_t)nslots);
+        A.io(&dnm, (size_t)nslots, (const int*)hnm.data(), (size_t)nslots, hnm.data(), (size_t)nslots);
+        for (int s = 0; s < nslots; s++) {                                        // [slot][cap] / [slot][qcap] blocks, each slot's rows from its own host arrays
+            const orbhip_proj_slot& S = slots[s];
+            orbhip_keypoint* k = nullptr; uint8_t *d = nullptr, *qd = nullptr; orbhip_proj_query* q = nullptr; float* ur = nullptr; unsigned char* bl = nullptr; int* fq = nullptr;
+            A.io(&k, C, S.kps, (size_t)S.n); A.io(&d, C * 32, S.desc, (size_t)S.n * 32); A.io(&q, Q, S.queries, (size_t)S.nq); A.io(&qd, Q * 32, S.query_desc, (size_t)S.nq * 32);
+            if (any_ur) A.io(&ur, C, S.u_right ? S.u_right : no_ur.data(), (size_t)S.n);
+            if (any_bl) A.io(&bl, C, (const unsigned char*)(S.blocked ? S.blocked : no_bl.data()), (size_t)S.n);
+            A.io(&fq, C, (const int*)nullptr, 0, S.feature_query, (size_t)S.n);
+            ProjParams& J = hJ[s]; memset(&J, 0, sizeof J);
+            J.kp = k; J.desc = d; J.u_right = S.u_right ? ur : nullptr; J.n = S.n; J.q = q; J.qdesc = qd; J.nq = S.nq; J.blocked_in = S.blocked ? bl : nullptr; J.feature_query = fq;
+        }
+        A.take(&dgs, (size_t)nslots * (ORBHIP_GRID_CELLS + 1)); A.take(&dgi, nslots * C); A.take(&dgxy, nslots * C); A.take(&dnc, nslots * Q); A.take(&dev, nslots * Q);
+        A.take(&dcand, nslots * Q * C); A.take(&dtop, nslots * Q * 5);
+        if (orbhip_proj_select_big(cap)) A.take(&dbig, nslots * 4 * C);      // the select kernel's per-feature tables when the largest slot's do not fit LDS
+        for (int s = 0; s < nslots; s++) {                                        // (hJ is read when the arena is uploaded, after this pass has filled in the addresses)
             ProjParams& J = hJ[s];
             J.big_ws = dbig ? dbig + s * 4 * C : nullptr;
             J.min_x = bounds->min_x; J.min_y = bounds->min_y; J.max_x = bounds->max_x; J.max_y = bounds->max_y;
@@ -1605,89 +1655,77 @@ extern "C" orbhip_status orbhip_search_by_projection_batch(int device, int nslot
             J.cand = dcand + s * Q * C; J.ncand = dnc + s * Q; J.cand_stride = cap; J.top = dtop + s * Q * 5; J.nmatches = dnm + s; J.events = dev + s * Q;
             J.mode = mode; J.nnratio = nnratio; J.th_high = th_high; J.check_ori = check_ori;
         }
-    }
-    TRY(arena_upload(ts));
-    if (e == hipSuccess) {
+    }, [&] {
         // Frame::AssignFeaturesToGrid of every slot: the grid kernel indexes [slot][stride]
-        for (int s = 0; s < nslots; s++) {
-            MatchParams M; memset(&M, 0, sizeof M);
-            M.kp2 = hJ[s].kp; M.n2 = dn + s; M.cap = cap; M.min_x = bounds->min_x; M.min_y = bounds->min_y; M.max_x = bounds->max_x; M.max_y = bounds->max_y;
-            M.grid_start = dgs + (size_t)s * (ORBHIP_GRID_CELLS + 1); M.grid_items = dgi + s * C; M.grid_xy = dgxy + s * C; M.grid_all_levels = 1;
-            orbhip_launch_match_grid(M, 1, ts);
-        }
+        for (int s = 0; s < nslots; s++) launch_feature_grid(hJ[s].kp, dn + s, cap, *bounds, dgs + (size_t)s * (ORBHIP_GRID_CELLS + 1), dgi + s * C, dgxy + s * C, 1, 0, ts);
         const float gwInv = (float)ORBHIP_GRID_COLS / (bounds->max_x - bounds->min_x), ghInv = (float)ORBHIP_GRID_ROWS / (bounds->max_y - bounds->min_y);
         orbhip_launch_proj_batch(dJ, nslots, qcap, cap, gwInv, ghInv, ts);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(ts));
-    if (e != hipSuccess) (void)hipStreamSynchronize(ts);            // never leave a copy in flight on the per-thread mirrors
-#undef TRY
+    });
     if (e != hipSuccess) return fail(ORBHIP_ERR_HIP, "search_by_projection_batch: %s", hipGetErrorString(e));
     for (int s = 0; s < nslots; s++) slots[s].nmatches = hnm[s];
     return ORBHIP_OK;
 }
 
-static orbhip_status search_best_in_window_impl(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right, int n, const orbhip_bounds* bounds,
-                                                const float* inv_level_sigma2, int nlevels, const orbhip_best_query* queries, const uint8_t* query_desc, int nq,
-                                                const orbhip_projection* P, const orbhip_map_point* points, orbhip_best_query* queries_out,
-                                                int chi2_gate, int32_t* best_idx, int32_t* best_dist)
+// inv_level_sigma2 / nlevels: mvInvLevelSigma2 of the frame's extractor (a context's frame: its own)
+static orbhip_status search_best_in_window(const SearchFrame& F, const float* inv_level_sigma2, int nlevels, const orbhip_best_query* queries, const uint8_t* query_desc, int nq,
+                                           const orbhip_projection* P, const orbhip_map_point* points, orbhip_best_query* queries_out,
+                                           int chi2_gate, int32_t* best_idx, int32_t* best_dist)
 {
     OrbApiTimer api_timer;
-    if (n < 0 || nq < 0 || (nq > 0 && ((!queries && !points) || !query_desc || !best_idx || !best_dist)) || (n > 0 && (!kps || !desc)) || !bounds || !(bounds->max_x > bounds->min_x) || !(bounds->max_y > bounds->min_y) ||
-        (chi2_gate && (!inv_level_sigma2 || nlevels < 1)) || (points && !projection_ok(P))) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; }
+    const int n = F.n;
+    if (nq < 0 || (nq > 0 && ((!queries && !points) || !query_desc || !best_idx || !best_dist)) || (chi2_gate && (!inv_level_sigma2 || nlevels < 1)) || (points && !projection_ok(P)))
+        return fail(ORBHIP_ERR_INVALID, "bad argument");
+    no_match(best_idx, best_dist, nq);
     if (points) gated_out(queries_out, nq);
     if (n == 0 || nq == 0) return ORBHIP_OK;
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    orbhip_keypoint* dk = nullptr; uint8_t *dd = nullptr, *dqd = nullptr; float *dur = nullptr, *dsg = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dbi = nullptr, *dbd = nullptr;
+    if (F.on_host && !device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    HIPCHK(hipSetDevice(F.device));
+    const hipStream_t s = F.on_host ? orbhip_thread_stream(F.device) : F.stream;
+    const orbhip_keypoint* dk = F.kps; const uint8_t* dd = F.desc; const float* dur = F.u_right;      // (host arrays: replaced by their copies)
+    uint8_t* dqd = nullptr; float* dsg = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dbi = nullptr, *dbd = nullptr;
     float2* dgxy = nullptr; orbhip_best_query* dq = nullptr; orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
     const int hn[2] = {n, 0};
-    TRY(arena_layout(device, [&](Arena& A) {
-        A.io(&dk, n, kps, n); A.io(&dd, (size_t)n * 32, desc, (size_t)n * 32); A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32); A.io(&dn, 8, hn, 2);
+    const hipError_t e = arena_call(F.device, s, [&](Arena& A) {
+        if (F.on_host) { arena_in(A, &dk, F.kps, n); arena_in(A, &dd, F.desc, (size_t)n * 32); }
+        A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32); A.io(&dn, 8, hn, 2);
         if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, P, 1); if (queries_out) A.io(&dq, nq, (const orbhip_best_query*)nullptr, 0, queries_out, nq); }
         else A.io(&dq, nq, queries, nq);
-        if (u_right) A.io(&dur, n, u_right, n);
+        if (F.on_host && F.u_right) arena_in(A, &dur, F.u_right, n);
         if (inv_level_sigma2 && nlevels > 0) A.io(&dsg, nlevels, inv_level_sigma2, nlevels);
         A.io(&dbi, nq, (const int*)nullptr, 0, best_idx, nq); A.io(&dbd, nq, (const int*)nullptr, 0, best_dist, nq);
         A.take(&dgs, ORBHIP_GRID_CELLS + 1); A.take(&dgi, n); A.take(&dgxy, n);
-    }));
-    TRY(arena_upload(ts));
-    if (e == hipSuccess) {
-        MatchParams M; memset(&M, 0, sizeof M);
-        M.kp2 = dk; M.n2 = dn; M.cap = n; M.min_x = bounds->min_x; M.min_y = bounds->min_y; M.max_x = bounds->max_x; M.max_y = bounds->max_y; M.grid_start = dgs; M.grid_items = dgi; M.grid_xy = dgxy; M.grid_all_levels = 1;
-        orbhip_launch_match_grid(M, 1, ts);
+    }, [&] {
+        const int* gs = F.grid_start; const int* gi = F.grid_items; const float2* gxy = F.grid_xy;
+        if (!gs) { launch_feature_grid(dk, dn, n, F.bounds, dgs, dgi, dgxy, 1, 0, s); gs = dgs; gi = dgi; gxy = dgxy; }
+        if (F.want_grid) *F.want_grid = true;
         BestParams B; memset(&B, 0, sizeof B);
-        B.kp = dk; B.desc = dd; B.u_right = dur; B.inv_level_sigma2 = dsg; B.grid_start = dgs; B.grid_items = dgi; B.grid_xy = dgxy;
+        B.kp = dk; B.desc = dd; B.u_right = dur; B.inv_level_sigma2 = dsg; B.grid_start = gs; B.grid_items = gi; B.grid_xy = gxy;
         B.q = dq; B.qdesc = dqd; B.nq = nq; B.chi2_gate = chi2_gate; B.best_idx = dbi; B.best_dist = dbd;
         B.pts = dpts; B.proj = dP; B.q_out = points ? dq : nullptr;
-        B.min_x = bounds->min_x; B.gw_inv = (float)ORBHIP_GRID_COLS / (float)(bounds->max_x - bounds->min_x);      // as orbhip_launch_match_grid lays the grid out
-        orbhip_launch_best_in_window(B, ts);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(ts));
-    if (e != hipSuccess) (void)hipStreamSynchronize(ts);            // never leave a copy in flight on the per-thread mirrors
-#undef TRY
-    orbhip_status st = ORBHIP_OK;
-    if (e != hipSuccess) st = fail(ORBHIP_ERR_HIP, "search_best_in_window: %s", hipGetErrorString(e));
-    return st;
+        B.min_x = F.bounds.min_x; B.gw_inv = (float)ORBHIP_GRID_COLS / (float)(F.bounds.max_x - F.bounds.min_x);      // as orbhip_launch_match_grid lays the grid out
+        orbhip_launch_best_in_window(B, s);
+    });
+    return e == hipSuccess ? ORBHIP_OK : fail(ORBHIP_ERR_HIP, F.on_host ? "search_best_in_window: %s" : "search_best_in_window_frame: %s", hipGetErrorString(e));
 }
 extern "C" orbhip_status orbhip_search_best_in_window_bounds(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right, int n, const orbhip_bounds* bounds,
                                                       const float* inv_level_sigma2, int nlevels, const orbhip_best_query* queries, const uint8_t* query_desc, int nq,
                                                       int chi2_gate, int32_t* best_idx, int32_t* best_dist)
 {
-    if (nq > 0 && !queries) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    return search_best_in_window_impl(device, kps, desc, u_right, n, bounds, inv_level_sigma2, nlevels, queries, query_desc, nq, nullptr, nullptr, nullptr, chi2_gate, best_idx, best_dist);
+    SearchFrame F; const orbhip_status st = host_frame(device, kps, desc, u_right, n, bounds, &F); if (st != ORBHIP_OK) return st;
+    return search_best_in_window(F, inv_level_sigma2, nlevels, queries, query_desc, nq, nullptr, nullptr, nullptr, chi2_gate, best_idx, best_dist);
 }
 extern "C" orbhip_status orbhip_project_best_in_window_bounds(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right, int n, const orbhip_bounds* bounds,
                                                               const float* inv_level_sigma2, int nlevels, const orbhip_projection* proj, const orbhip_map_point* points, const uint8_t* point_desc, int np,
                                                               int chi2_gate, int32_t* best_idx, int32_t* best_dist, orbhip_best_query* queries_out)
 {
-    if (np > 0 && (!points || !proj)) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    return search_best_in_window_impl(device, kps, desc, u_right, n, bounds, inv_level_sigma2, nlevels, nullptr, point_desc, np, np > 0 ? proj : nullptr, np > 0 ? points : nullptr, queries_out, chi2_gate, best_idx, best_dist);
+    SearchFrame F; const orbhip_status st = host_frame(device, kps, desc, u_right, n, bounds, &F); if (st != ORBHIP_OK) return st;
+    return search_best_in_window(F, inv_level_sigma2, nlevels, nullptr, point_desc, np, np > 0 ? proj : nullptr, np > 0 ? points : nullptr, queries_out, chi2_gate, best_idx, best_dist);
+}
+extern "C" orbhip_status orbhip_search_best_in_window_frame(orbhip_ctx* c, int frame, int n, int use_u_right, const orbhip_best_query* queries, const uint8_t* query_desc, int nq,
+                                                            int chi2_gate, int32_t* best_idx, int32_t* best_dist)
+{
+    SearchFrame F; const orbhip_status st = frame_args(c, frame, n, use_u_right, &F); if (st != ORBHIP_OK) return st;
+    return search_best_in_window(F, c->is2.data(), c->L, queries, query_desc, nq, nullptr, nullptr, nullptr, chi2_gate, best_idx, best_dist);
 }
 
 // Several key frames in one pass (Fuse over all targets): [slot][cap] key point / descriptor / grid blocks in one arena; the feature grids of all slots are
@@ -1702,7 +1740,6 @@ struct BestSlotIn {
 static orbhip_status search_best_in_window_batch_impl(int device, int nslots, BestSlotIn* slots, int chi2_gate, bool shared = false, const uint64_t* skip = nullptr)
 {
     OrbApiTimer api_timer;
-    if (nslots < 0 || (nslots > 0 && !slots)) return fail(ORBHIP_ERR_INVALID, "bad argument");
     if (shared) {
         orbhip_tl_held_valid = false;                                                   // whatever an earlier call left held is not THIS call's (also when nothing is live below)
         if (nslots > 64) return fail(ORBHIP_ERR_INVALID, "at most 64 slots share one set of points");
@@ -1717,7 +1754,7 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
         if (S.n < 0 || S.nq < 0 || (S.nq > 0 && ((!S.queries && !S.points) || !S.query_desc || !S.best_idx || !S.best_dist)) || (S.n > 0 && (!S.kps || !S.desc)) ||
             !(S.bounds.max_x > S.bounds.min_x) || !(S.bounds.max_y > S.bounds.min_y) || (chi2_gate && (!S.inv_level_sigma2 || S.nlevels < 1)) || (S.nq > 0 && S.points && !projection_ok(S.proj)))
             return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
-        for (int i = 0; i < S.nq; i++) { S.best_idx[i] = -1; S.best_dist[i] = 256; }
+        no_match(S.best_idx, S.best_dist, S.nq);
         if (S.n == 0 || S.nq == 0) continue;
         live.push_back(s); cap = std::max(cap, S.n);
     }
@@ -1729,7 +1766,7 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
         }
         return ORBHIP_OK;
     }
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    if (!device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
     HIPCHK(hipSetDevice(device));
     hipStream_t ts = orbhip_thread_stream(device);
     cap = (cap + 63) & ~63;                                  // 64 key points = 7 x 256 bytes: the arena's 256-byte blocks then lie exactly cap records apart ([slot][cap])
@@ -1741,9 +1778,7 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
     BestParams* dB = nullptr; int *dpref = nullptr, *dn = nullptr, *dgs = nullptr, *dgi = nullptr; float2* dgxy = nullptr; orbhip_keypoint* dk0 = nullptr;
     uint8_t* dqd0 = nullptr; orbhip_map_point* dpts0 = nullptr; unsigned long long* dskip = nullptr;          // shared: the one copy of the points
     size_t held_floor = 0;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
-    TRY(arena_layout(device, [&](Arena& A) {
+    const hipError_t e = arena_call(device, ts, [&](Arena& A) {
         A.io(&dB, (size_t)NL, (const BestParams*)hB.data(), (size_t)NL);
         A.io(&dpref, (size_t)NL + 1, (const int*)pref.data(), (size_t)NL + 1);
         A.io(&dn, (size_t)NL, (const int*)hn.data(), (size_t)NL);
@@ -1781,27 +1816,16 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
             B.best_idx = dbi; B.best_dist = dbd;
         }
         A.take(&dgs, (size_t)NL * (ORBHIP_GRID_CELLS + 1)); A.take(&dgi, NL * C); A.take(&dgxy, NL * C);
+        for (int k = 0; k < NL; k++) { hB[k].grid_start = dgs + (size_t)k * (ORBHIP_GRID_CELLS + 1); hB[k].grid_items = dgi + k * C; hB[k].grid_xy = dgxy + k * C; }
         if (shared) {                                                                   // room for the held entry's queries behind everything: it never reallocates
             held_floor = A.off; uint8_t* pad = nullptr; A.take(&pad, (size_t)slots[live[0]].nq * (sizeof(orbhip_map_point) + 32 + 8) + 4096);
         }
-    }));
-    for (int k = 0; k < NL && e == hipSuccess; k++) { hB[k].grid_start = dgs + (size_t)k * (ORBHIP_GRID_CELLS + 1); hB[k].grid_items = dgi + k * C; hB[k].grid_xy = dgxy + k * C; }
-    TRY(arena_upload(ts));
-    if (e == hipSuccess) {
-        for (int k = 0; k < (same_bounds ? 1 : NL); k++) {
-            const orbhip_bounds& b = slots[live[k]].bounds;
-            MatchParams M; memset(&M, 0, sizeof M);
-            M.kp2 = dk0; M.n2 = dn; M.cap = cap; M.min_x = b.min_x; M.min_y = b.min_y; M.max_x = b.max_x; M.max_y = b.max_y; M.grid_start = dgs; M.grid_items = dgi; M.grid_xy = dgxy; M.grid_all_levels = 1; M.slot0 = k;
-            orbhip_launch_match_grid(M, same_bounds ? NL : 1, ts);
-        }
+    }, [&] {
+        for (int k = 0; k < (same_bounds ? 1 : NL); k++) launch_feature_grid(dk0, dn, cap, slots[live[k]].bounds, dgs, dgi, dgxy, same_bounds ? NL : 1, k, ts);
         orbhip_launch_best_in_window_batch(dB, dpref, NL, pref[NL], ts);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(ts));
-    if (e != hipSuccess) (void)hipStreamSynchronize(ts);
-#undef TRY
+    });
     if (e != hipSuccess) {
-        for (int k = 0; k < NL; k++) { BestSlotIn& S = slots[live[k]]; for (int i = 0; i < S.nq; i++) { S.best_idx[i] = -1; S.best_dist[i] = 256; } }
+        for (int k = 0; k < NL; k++) no_match(slots[live[k]].best_idx, slots[live[k]].best_dist, slots[live[k]].nq);
         return fail(ORBHIP_ERR_HIP, "search_best_in_window_batch: %s", hipGetErrorString(e));
     }
     if (shared) {                                                                       // the slots stay where they are for orbhip_project_best_in_window_held
@@ -1821,31 +1845,23 @@ extern "C" orbhip_status orbhip_project_best_in_window_held(int device, int slot
     if (np < 0 || (np > 0 && (!points || !point_desc || !best_idx || !best_dist || !projection_ok(proj)))) return fail(ORBHIP_ERR_INVALID, "bad argument");
     if (!orbhip_tl_held_valid || g_held.device != device || slot < 0 || slot >= (int)g_held.live_of_slot.size())
         return fail(ORBHIP_ERR_INVALID, "no held slot %d: the calling thread's last scratch-using call was not orbhip_project_best_in_window_shared on this device", slot);
-    for (int i = 0; i < np; i++) { best_idx[i] = -1; best_dist[i] = 256; }
+    no_match(best_idx, best_dist, np);
     const int k = g_held.live_of_slot[(size_t)slot];
     if (k == -2) return fail(ORBHIP_ERR_INVALID, "held slot %d: its key frame did not travel (the shared call offered no points)", slot);
     if (k < 0 || np == 0) return ORBHIP_OK;                                             // (a slot without key points or a call without points: nothing to search)
     HIPCHK(hipSetDevice(device));
     hipStream_t ts = orbhip_thread_stream(device);
     uint8_t* dqd = nullptr; orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr; int *dbi = nullptr, *dbd = nullptr;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
-    TRY(arena_layout(device, [&](Arena& A) {
+    const hipError_t e = arena_call(device, ts, [&](Arena& A) {
         A.io(&dqd, (size_t)np * 32, point_desc, (size_t)np * 32); A.io(&dpts, np, points, np); A.io(&dP, 1, proj, 1);
         A.io(&dbi, np, (const int*)nullptr, 0, best_idx, np); A.io(&dbd, np, (const int*)nullptr, 0, best_dist, np);
-    }, g_held.floor));
-    if (e == hipErrorOutOfMemory) return fail(ORBHIP_ERR_INVALID, "the held scratch has no room for %d points", np);      // (the caller falls back to the full entry)
-    TRY(arena_upload(ts));
-    if (e == hipSuccess) {
+    }, [&] {
         BestParams B = g_held.B[(size_t)k];
         B.q = nullptr; B.qdesc = dqd; B.nq = np; B.chi2_gate = chi2_gate; B.pts = dpts; B.proj = dP; B.q_out = nullptr; B.best_idx = dbi; B.best_dist = dbd; B.skip = nullptr; B.skip_bit = 0;
         orbhip_launch_best_in_window(B, ts);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(ts));
-    if (e != hipSuccess) (void)hipStreamSynchronize(ts);
-#undef TRY
-    if (e != hipSuccess) { for (int i = 0; i < np; i++) { best_idx[i] = -1; best_dist[i] = 256; } return fail(ORBHIP_ERR_HIP, "project_best_in_window_held: %s", hipGetErrorString(e)); }
+    }, g_held.floor);
+    if (e == hipErrorOutOfMemory) return fail(ORBHIP_ERR_INVALID, "the held scratch has no room for %d points", np);      // (the caller falls back to the full entry)
+    if (e != hipSuccess) { no_match(best_idx, best_dist, np); return fail(ORBHIP_ERR_HIP, "project_best_in_window_held: %s", hipGetErrorString(e)); }
     return ORBHIP_OK;
 }
 extern "C" orbhip_status orbhip_search_best_in_window_batch(int device, int nslots, orbhip_best_slot* slots, int chi2_gate)
@@ -1859,7 +1875,8 @@ extern "C" orbhip_status orbhip_search_best_in_window_batch(int device, int nslo
     }
     return search_best_in_window_batch_impl(device, nslots, in.data(), chi2_gate);
 }
-extern "C" orbhip_status orbhip_project_best_in_window_batch(int device, int nslots, orbhip_project_best_slot* slots, int chi2_gate)
+// orbhip_project_best_in_window_batch / _shared: the slots' points projected on the device
+static orbhip_status project_best_in_window_slots(int device, int nslots, const orbhip_project_best_slot* slots, int chi2_gate, bool shared, const uint64_t* skip)
 {
     if (nslots < 0 || (nslots > 0 && !slots)) return fail(ORBHIP_ERR_INVALID, "bad argument");
     std::vector<BestSlotIn> in((size_t)nslots);
@@ -1868,139 +1885,15 @@ extern "C" orbhip_status orbhip_project_best_in_window_batch(int device, int nsl
         if (S.np > 0 && (!S.points || !S.proj)) return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
         in[s] = BestSlotIn{S.kps, S.desc, S.u_right, S.n, S.bounds, S.inv_level_sigma2, S.nlevels, nullptr, S.point_desc, S.np, S.np > 0 ? S.proj : nullptr, S.np > 0 ? S.points : nullptr, S.best_idx, S.best_dist};
     }
-    return search_best_in_window_batch_impl(device, nslots, in.data(), chi2_gate);
+    return search_best_in_window_batch_impl(device, nslots, in.data(), chi2_gate, shared, skip);
+}
+extern "C" orbhip_status orbhip_project_best_in_window_batch(int device, int nslots, orbhip_project_best_slot* slots, int chi2_gate)
+{
+    return project_best_in_window_slots(device, nslots, slots, chi2_gate, false, nullptr);
 }
 extern "C" orbhip_status orbhip_project_best_in_window_shared(int device, int nslots, orbhip_project_best_slot* slots, const uint64_t* skip, int chi2_gate)
 {
-    if (nslots < 0 || (nslots > 0 && !slots)) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    std::vector<BestSlotIn> in((size_t)nslots);
-    for (int s = 0; s < nslots; s++) {
-        const orbhip_project_best_slot& S = slots[s];
-        if (S.np > 0 && (!S.points || !S.proj)) return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
-        in[s] = BestSlotIn{S.kps, S.desc, S.u_right, S.n, S.bounds, S.inv_level_sigma2, S.nlevels, nullptr, S.point_desc, S.np, S.np > 0 ? S.proj : nullptr, S.np > 0 ? S.points : nullptr, S.best_idx, S.best_dist};
-    }
-    return search_best_in_window_batch_impl(device, nslots, in.data(), chi2_gate, true, skip);
-}
-
-// The two searches above on a frame that is still on the device: key points (mvKeysUn with a distorted camera attached), descriptors
-// and — if asked for — mvuRight of the last stereo / RGB-D step are read where the extraction left them; only the queries travel.
-static orbhip_status frame_args(orbhip_ctx* c, int frame, int n, int use_u_right, const orbhip_keypoint** kp, const uint8_t** desc, const float** ur)
-{
-    if (!c) return fail(ORBHIP_ERR_INVALID, "null context");
-    if (frame < 0 || frame >= c->last_nimg) return fail(ORBHIP_ERR_INVALID, "frame %d outside the %d frames of the last extraction", frame, c->last_nimg);
-    if (n < 0 || n > c->out_cap) return fail(ORBHIP_ERR_INVALID, "n %d outside 0..%d", n, c->out_cap);
-    if (use_u_right && !c->d_last_uright) return fail(ORBHIP_ERR_INVALID, "no mvuRight on the device: run orbhip_compute_stereo_matches / orbhip_compute_stereo_from_rgbd on this context first");
-    *kp = (c->distorted ? c->d_out_kpun : c->d_out_kp)[c->cur] + (size_t)frame * c->out_cap;
-    *desc = c->d_out_desc[c->cur] + (size_t)frame * c->out_cap * 32;
-    *ur = use_u_right ? c->d_last_uright + (size_t)frame * c->out_cap : nullptr;
-    return ORBHIP_OK;
-}
-static orbhip_status search_by_projection_frame_impl(orbhip_ctx* c, int frame, int n, int use_u_right, const uint8_t* blocked,
-                                                     const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
-                                                     const orbhip_projection* P, const orbhip_map_point* points, orbhip_proj_query* queries_out,
-                                                     int mode, float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches)
-{
-    OrbApiTimer api_timer;
-    const orbhip_keypoint* dk = nullptr; const uint8_t* dd = nullptr; const float* dur = nullptr;
-    orbhip_status st = frame_args(c, frame, n, use_u_right, &dk, &dd, &dur); if (st != ORBHIP_OK) return st;
-    if (nq < 0 || !nmatches || (n > 0 && !feature_query) || (nq > 0 && ((!queries && !points) || !query_desc)) || (mode != 0 && mode != 1) || (points && !projection_ok(P))) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    *nmatches = 0;
-    for (int i = 0; i < n; i++) feature_query[i] = -1;
-    if (points) gated_out(queries_out, nq);
-    if (n == 0 || nq == 0) return ORBHIP_OK;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    uint8_t* dqd = nullptr; unsigned char* dbl_in = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dfq = nullptr, *dev = nullptr, *dbig = nullptr;
-    float2* dgxy = nullptr; orbhip_proj_query* dq = nullptr; unsigned* dcand = nullptr; unsigned* dtop = nullptr;
-    orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
-    const int hn[2] = {n, 0}; int hres[2] = {0, 0};
-    TRY(arena_layout(c->cfg.device, [&](Arena& A) {
-        A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32);
-        if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, P, 1); A.io(&dq, nq, (const orbhip_proj_query*)nullptr, 0, queries_out, queries_out ? nq : 0); }
-        else A.io(&dq, nq, queries, nq);
-        if (blocked) A.io(&dbl_in, n, blocked, n);
-        A.io(&dn, 8, hn, 2, hres, 2);
-        A.io(&dfq, n, (const int*)nullptr, 0, feature_query, n);
-        A.take(&dgs, ORBHIP_GRID_CELLS + 1); A.take(&dgi, n); A.take(&dgxy, n); A.take(&dnc, nq); A.take(&dev, nq);
-        A.take(&dcand, (size_t)nq * n); A.take(&dtop, (size_t)nq * 5);
-        if (orbhip_proj_select_big(n)) A.take(&dbig, (size_t)4 * n);
-    }));
-    TRY(arena_upload(c->stream));
-    if (e == hipSuccess) {
-        MatchParams M; memset(&M, 0, sizeof M);
-        M.kp2 = dk; M.n2 = dn; M.cap = n; M.min_x = c->bounds.min_x; M.min_y = c->bounds.min_y; M.max_x = c->bounds.max_x; M.max_y = c->bounds.max_y; M.grid_start = dgs; M.grid_items = dgi; M.grid_xy = dgxy; M.grid_all_levels = 1;
-        // the grid of this frame was built behind its extraction (frame epilogue, same stream): take it; from now on it always will be
-        if (frame == 0 && c->fgrid_valid && c->fgrid_cur == c->cur && c->last_n_valid && c->last_n[0] == n) { dgs = c->d_fgrid_start; dgi = c->d_fgrid_items; dgxy = c->d_fgrid_xy; }
-        else orbhip_launch_match_grid(M, 1, c->stream);
-        if (c->last_nimg == 1 || c->pair_mode) c->want_fgrid = true;
-        ProjParams J; memset(&J, 0, sizeof J);
-        J.kp = dk; J.desc = dd; J.u_right = dur; J.n = n; J.min_x = M.min_x; J.min_y = M.min_y; J.max_x = M.max_x; J.max_y = M.max_y; J.grid_start = dgs; J.grid_items = dgi; J.grid_xy = dgxy;
-        J.q = dq; J.qdesc = dqd; J.nq = nq; J.cand = dcand; J.ncand = dnc; J.cand_stride = n; J.top = dtop;
-        J.pts = dpts; J.proj = dP; J.q_out = dq;
-        J.blocked_in = dbl_in; J.blocked_out = nullptr; J.feature_query = dfq; J.nmatches = dn + 1; J.events = dev;
-        J.mode = mode; J.nnratio = nnratio; J.th_high = th_high; J.check_ori = check_ori; J.big_ws = dbig;
-        orbhip_launch_proj(J, c->stream);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(c->stream));
-    if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);            // never leave a copy in flight on the per-thread mirrors
-    if (e == hipSuccess) *nmatches = hres[1];
-#undef TRY
-    return e == hipSuccess ? ORBHIP_OK : fail(ORBHIP_ERR_HIP, "search_by_projection_frame: %s", hipGetErrorString(e));
-}
-extern "C" orbhip_status orbhip_search_by_projection_frame(orbhip_ctx* c, int frame, int n, int use_u_right, const uint8_t* blocked,
-                                                           const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
-                                                           int mode, float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches)
-{
-    if (nq > 0 && !queries) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    return search_by_projection_frame_impl(c, frame, n, use_u_right, blocked, queries, query_desc, nq, nullptr, nullptr, nullptr, mode, nnratio, th_high, check_ori, feature_query, nmatches);
-}
-extern "C" orbhip_status orbhip_project_search_frame(orbhip_ctx* c, int frame, int n, int use_u_right, const uint8_t* blocked,
-                                                     const orbhip_projection* proj, const orbhip_map_point* points, const uint8_t* point_desc, int np,
-                                                     float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches, orbhip_proj_query* queries_out)
-{
-    if (np > 0 && (!points || !proj)) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    return search_by_projection_frame_impl(c, frame, n, use_u_right, blocked, nullptr, point_desc, np, np > 0 ? proj : nullptr, np > 0 ? points : nullptr, queries_out, 1, nnratio, th_high, check_ori, feature_query, nmatches);
-}
-extern "C" orbhip_status orbhip_search_best_in_window_frame(orbhip_ctx* c, int frame, int n, int use_u_right, const orbhip_best_query* queries, const uint8_t* query_desc, int nq,
-                                                            int chi2_gate, int32_t* best_idx, int32_t* best_dist)
-{
-    OrbApiTimer api_timer;
-    const orbhip_keypoint* dk = nullptr; const uint8_t* dd = nullptr; const float* dur = nullptr;
-    orbhip_status st = frame_args(c, frame, n, use_u_right, &dk, &dd, &dur); if (st != ORBHIP_OK) return st;
-    if (nq < 0 || (nq > 0 && (!queries || !query_desc || !best_idx || !best_dist))) return fail(ORBHIP_ERR_INVALID, "bad argument");
-    for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; }
-    if (n == 0 || nq == 0) return ORBHIP_OK;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    uint8_t* dqd = nullptr; float* dsg = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dbi = nullptr, *dbd = nullptr; float2* dgxy = nullptr; orbhip_best_query* dq = nullptr;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
-    const int hn[2] = {n, 0};
-    TRY(arena_layout(c->cfg.device, [&](Arena& A) {
-        A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32); A.io(&dq, nq, queries, nq); A.io(&dn, 8, hn, 2);
-        A.io(&dsg, c->L, (const float*)c->is2.data(), (size_t)c->L);                               // mvInvLevelSigma2 of this extractor
-        A.io(&dbi, nq, (const int*)nullptr, 0, best_idx, nq); A.io(&dbd, nq, (const int*)nullptr, 0, best_dist, nq);
-        A.take(&dgs, ORBHIP_GRID_CELLS + 1); A.take(&dgi, n); A.take(&dgxy, n);
-    }));
-    TRY(arena_upload(c->stream));
-    if (e == hipSuccess) {
-        MatchParams M; memset(&M, 0, sizeof M);
-        M.kp2 = dk; M.n2 = dn; M.cap = n; M.min_x = c->bounds.min_x; M.min_y = c->bounds.min_y; M.max_x = c->bounds.max_x; M.max_y = c->bounds.max_y; M.grid_start = dgs; M.grid_items = dgi; M.grid_xy = dgxy; M.grid_all_levels = 1;
-        if (frame == 0 && c->fgrid_valid && c->fgrid_cur == c->cur && c->last_n_valid && c->last_n[0] == n) { dgs = c->d_fgrid_start; dgi = c->d_fgrid_items; dgxy = c->d_fgrid_xy; }   // frame epilogue
-        else orbhip_launch_match_grid(M, 1, c->stream);
-        if (c->last_nimg == 1 || c->pair_mode) c->want_fgrid = true;
-        BestParams B; memset(&B, 0, sizeof B);
-        B.kp = dk; B.desc = dd; B.u_right = dur; B.inv_level_sigma2 = dsg; B.grid_start = dgs; B.grid_items = dgi; B.grid_xy = dgxy;
-        B.q = dq; B.qdesc = dqd; B.nq = nq; B.chi2_gate = chi2_gate; B.best_idx = dbi; B.best_dist = dbd;
-        B.min_x = c->bounds.min_x; B.gw_inv = (float)ORBHIP_GRID_COLS / (float)(c->bounds.max_x - c->bounds.min_x);
-        orbhip_launch_best_in_window(B, c->stream);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(c->stream));
-    if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);            // never leave a copy in flight on the per-thread mirrors
-#undef TRY
-    return e == hipSuccess ? ORBHIP_OK : fail(ORBHIP_ERR_HIP, "search_best_in_window_frame: %s", hipGetErrorString(e));
+    return project_best_in_window_slots(device, nslots, slots, chi2_gate, true, skip);
 }
 
 // ---------------------------------------------------------------------------------------------- stereo
@@ -2178,7 +2071,7 @@ extern "C" orbhip_status orbhip_undistort_points(int device, const orbhip_camera
     OrbApiTimer api_timer;
     if (!camera_ok(cam) || n < 0 || (n > 0 && (!xy || !xy_out))) return fail(ORBHIP_ERR_INVALID, "bad argument");
     if (n == 0) return ORBHIP_OK;
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    if (!device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
     HIPCHK(hipSetDevice(device));
     hipStream_t ts = orbhip_thread_stream(device);
     float *din = nullptr, *dout = nullptr;
@@ -2439,7 +2332,7 @@ extern "C" orbhip_status orbhip_hamming_nn(int device, const uint8_t* q, int nq,
 {
     if (nq < 0 || ndb < 0 || (nq > 0 && (!q || !best_idx || !best_dist || !second_dist)) || (ndb > 0 && !db)) return fail(ORBHIP_ERR_INVALID, "bad argument");
     if (nq == 0) return ORBHIP_OK;
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    if (!device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
     HIPCHK(hipSetDevice(device));
     uint8_t *dq = nullptr, *ddb = nullptr; long long* dbi = nullptr; int *dbd = nullptr, *dsd = nullptr;
     orbhip_status st = ORBHIP_OK;
@@ -2471,7 +2364,7 @@ extern "C" orbhip_status orbhip_search_for_initialization_bounds(int device, con
     *nmatches = 0;
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (n1 == 0) return ORBHIP_OK;
-    int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    if (!device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
     HIPCHK(hipSetDevice(device));
     hipStream_t ts = orbhip_thread_stream(device);
     // Frame members flattened: level-0 keypoints of F1 in index order (the loop at ORBmatcher.cc:418-423 skips the rest)
@@ -2480,10 +2373,8 @@ extern "C" orbhip_status orbhip_search_for_initialization_bounds(int device, con
     const int cap = std::max(std::max(n1, n2), 1), l0cap = std::max((int)list1.size(), 1), cstride = std::max(n2l0, 1);
     orbhip_keypoint *dk1 = nullptr, *dk2 = nullptr; uint8_t *dd1 = nullptr, *dd2 = nullptr; int *dn = nullptr, *dlist = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dm12 = nullptr, *dbig = nullptr; float2* dgxy = nullptr;
     unsigned* dcand = nullptr; unsigned* dtop = nullptr; float* dprev = nullptr;
-    hipError_t e = hipSuccess;
-#define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
     const int hn[4] = {n1, n2, (int)list1.size(), 0}; int hres[4] = {0, 0, 0, 0};
-    TRY(arena_layout(device, [&](Arena& A) {
+    const hipError_t e = arena_call(device, ts, [&](Arena& A) {
         A.io(&dk1, cap, kps1, n1); A.io(&dk2, cap, kps2, n2); A.io(&dd1, (size_t)cap * 32, desc1, (size_t)n1 * 32); A.io(&dd2, (size_t)cap * 32, desc2, (size_t)n2 * 32);
         A.io(&dlist, l0cap, (const int*)list1.data(), list1.size());
         A.io(&dn, 8, hn, 4, hres, 4);                          // counts in, [3] = nmatches out
@@ -2492,23 +2383,16 @@ extern "C" orbhip_status orbhip_search_for_initialization_bounds(int device, con
         A.take(&dgs, ORBHIP_GRID_CELLS + 1); A.take(&dgi, cap); A.take(&dgxy, cap); A.take(&dnc, l0cap);
         A.take(&dcand, (size_t)l0cap * cstride); A.take(&dtop, (size_t)l0cap * 5);
         if (orbhip_match_select_big(cap, l0cap)) A.take(&dbig, orbhip_match_select_ints(cap, l0cap));      // the select kernel's tables when they do not fit LDS
-    }));
-    TRY(arena_upload(ts));
-    if (e == hipSuccess) {
+    }, [&] {
         MatchParams M; memset(&M, 0, sizeof M);
         M.kp1 = dk1; M.desc1 = dd1; M.n1 = dn; M.n1_lvl0 = dn + 2; M.kp2 = dk2; M.desc2 = dd2; M.n2 = dn + 1; M.lvl_stride = 0; M.list1 = dlist; M.prev_from_kp1 = 0;
         M.cap = cap; M.min_x = bounds->min_x; M.min_y = bounds->min_y; M.max_x = bounds->max_x; M.max_y = bounds->max_y; M.grid_start = dgs; M.grid_items = dgi; M.grid_xy = dgxy; M.cand = dcand; M.top = dtop; M.ncand = dnc; M.cand_stride = cstride; M.lvl0_cap = l0cap;
         M.prev = dprev; M.matches12 = dm12; M.nmatches = dn + 3; M.window = window; M.nnratio = nnratio; M.check_ori = check_ori; M.big_ws = dbig;
         orbhip_launch_match_grid(M, 1, ts); orbhip_launch_match_candidates(M, 1, ts); orbhip_launch_match_select(M, 1, ts);
-        e = hipGetLastError();
-    }
-    TRY(arena_download(ts));
-    if (e != hipSuccess) (void)hipStreamSynchronize(ts);            // never leave a copy in flight on the per-thread mirrors
-    if (e == hipSuccess) *nmatches = hres[3];
-#undef TRY
-    orbhip_status st = ORBHIP_OK;
-    if (e != hipSuccess) st = fail(ORBHIP_ERR_HIP, "search_for_initialization: %s", hipGetErrorString(e));
-    return st;
+    });
+    if (e != hipSuccess) return fail(ORBHIP_ERR_HIP, "search_for_initialization: %s", hipGetErrorString(e));
+    *nmatches = hres[3];
+    return ORBHIP_OK;
 }
 
 // the im_w / im_h forms: an undistorted camera, mnMinX = mnMinY = 0, mnMaxX = cols, mnMaxY = rows (Frame.cc:455-463)
