@@ -4,7 +4,7 @@
 //   k_hamming_nn / k_hamming_merge   brute-force 256-bit Hamming NN, queries in registers, DB rows broadcast from LDS,
 //                                    __popcll on 4 x u64 per pair (ORBmatcher::DescriptorDistance, ORBmatcher.cc:1647-1663;
 //                                    best/second idiom :102-114, :447-456).  Integer-VALU bound (v_xor + v_bcnt); small databases.
-//   k_hamming_nn_mfma                the same scan as +-1 i8 products on the matrix cores (databases from 32 K rows on)
+//   k_hamming_nn_fp4b                the same scan as +-1 FP4 products on the matrix cores (databases from 32 K rows on)
 //   k_match_grid                     Frame::AssignFeaturesToGrid (Frame.cc:230-245, 382-392): 64x48 buckets, keypoint order
 //   k_match_candidates               Frame::GetFeaturesInArea (Frame.cc:327-380) in canonical order + all Hamming distances,
 //                                    one wavefront per previous-frame keypoint; also records each key point's four best candidates
@@ -76,159 +76,62 @@ __global__ __launch_bounds__(NN_T) void k_hamming_nn(const unsigned long long* q
         }
 }
 
-// ---- the same scan on the matrix cores.  With descriptor bits as +-1, <a, b> = 256 - 2 * Hamming(a, b): the distance table of 32 DB rows x
-// 32 queries is one 32 x 32 x 256 i8 product (8 x v_mfma_i32_32x32x32_i8), exact, and the popcount formulation's ceiling (1.7e12 pair
-// distances/s, VALU-bound on v_xor + v_bcnt) does not apply.  A workgroup keeps 256 queries as B operands in registers (4 waves x 2 tiles of
-// 32 queries, lane = query) and streams its chunk of DB rows: 32 rows at a time are expanded from bits to +-1 bytes through a 256-entry LDS
-// table (once per workgroup, shared by its eight query tiles) and read back as A operands (lane = row, bytes = 16 bits of one dword).
-// The result leaves with lane = query, register = DB row, so the running (best, second) keys of a query are two registers of its lane.
-// The accumulators ARE the tile's keys, with no VALU work per pair: the queries are expanded to -+64 instead of -+1 and the C operand of the
-// first product of a tile is the constant 256 * 64 + row-in-tile, so that   acc = (256 - dot) * 64 + r = distance << 7 | r   (r < 64).
-// A v_min3 / v_med3 tournament picks the tile's two smallest, and only those two are turned into chunk keys distance << 13 | row-in-chunk
-// (three operations each) for   second = min(second, max(best, key)), best = min(best, key)
-// exactly as in k_hamming_nn, whose partial format and merge kernel are reused.
+// ---- the same scan on the FP4 matrix path (gfx950: v_mfma_scale_f32_32x32x64_f8f6f4).  With descriptor bits as +-1, <a, b> = 256 - 2 * Hamming(a, b), and
+// +-1 is exact in E2M1 (+1 = 0x2, -1 = 0xA; bit k of a byte -> nibble k: s_tab).  A descriptor is 256 nibbles = 8 x 16 bytes, a tile of 32 DB rows 4 KB:
+// [dword d of the row = 2 kb + h][row i] x 16 bytes.  Lane (j, h) of a wave holds query j of a 32-query tile as B operands, K block kb = dword 2 kb + h of
+// the query, with the SAME sign as the rows (set bit -> +1), and reads row j of the tile as A operands, the same dwords.  The rows' block scale is 2^0
+// (E8M0 127), the queries' 2^6 (133): a matching bit contributes +64, a differing one -64, and with C = 0 an accumulator is the similarity
+// sim = 64 (256 - 2 d) = 16384 - 128 d  of (row, query) - an integer of magnitude <= 2^14, exact in f32.  The result leaves with lane = query, register reg =
+// DB row (reg & 3) + 8 (reg >> 2) + 4 h of the tile.
+// KEYS.  A kept (tile, query tile) turns its similarities into the keys  d << 7 | row-in-tile = 16384 + row - sim  as floats.  Positive floats order like
+// their bit patterns: the v_min3 / v_med3 tournament runs on the raw registers and only the two winners are converted, into chunk keys
+// d << LCH | row-in-chunk, and merged into the query's running pair  second = min(second, max(best, key)), best = min(best, key)  exactly as in
+// k_hamming_nn, whose partial format and merge kernel are reused.  THRESHOLD: a tile matters to a query only if it holds a similarity ABOVE thr[t], i.e. a
+// distance strictly below the running second best - a later row at that distance has a larger key than it (rows ascend).
 typedef int nn_v4i __attribute__((vector_size(16)));
-typedef int nn_v16i __attribute__((vector_size(64)));
-#define NNM_QT 2                        // query tiles (of 32) per wavefront (3: 9.7 ms against 7.9 - a sixth workgroup column of padding; 4: spills)
-#define NNM_QG (4 * NNM_QT * 32)        // queries per workgroup
-#define ORBHIP_NN_DEFAULT 2             // form of the matrix-core scan orbhip_launch_hamming_nn takes (1 = i8, 2 = FP4 in the shape below: 5.3 ms against 8.0 for 2000 x 20 M, profiles/r05_exp_config5_fp4_shapes.jsonl)
-#define ORBHIP_NN_FP4_QT 4
-#define ORBHIP_NN_FP4_OCC 2
-#define ORBHIP_NN_FP4_LCH 15
-#define ORBHIP_NN_FP4_TPB 6
-__global__ __launch_bounds__(256, 2) void k_hamming_nn_mfma(const unsigned* q, int nq, const unsigned* db, long long ndb, long long base, NNPart* parts, int nchunks)
-{
-    __shared__ unsigned long long s_tab[256];                          // byte -> its 8 bits as +-1 bytes
-    __shared__ __attribute__((aligned(16))) unsigned s_a[2][16 * 32 * 4];   // expanded DB tile: [K block kb][lane half h][row i] x 16 bytes, double-buffered
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), chunk = blockIdx.y;
-    {
-        unsigned long long e = 0;
-#pragma unroll
-        for (int t = 0; t < 8; t++) e |= (unsigned long long)(((tid >> t) & 1) ? 0x01u : 0xffu) << (8 * t);
-        s_tab[tid] = e;
-    }
-    __syncthreads();
-    const int j = lane & 31, h = lane >> 5;
-    // ---- the wave's queries as B operands: lane (j, h), K block kb = bits 16h .. 16h+15 of dword kb of query j
-    nn_v4i B[NNM_QT][8];
-    int qidx[NNM_QT];
-#pragma unroll
-    for (int t = 0; t < NNM_QT; t++) {
-        qidx[t] = blockIdx.x * NNM_QG + (wave * NNM_QT + t) * 32 + j;
-        const unsigned* qp = q + (long long)min(qidx[t], nq - 1) * 8;
-#pragma unroll
-        for (int kb = 0; kb < 8; kb++) {
-            const unsigned half = (qp[kb] >> (16 * h)) & 0xffffu;
-            // the queries carry the opposite sign and the weight 64: table byte 0x01 (bit set) -> 0xc0 = -64, 0xff (bit clear) -> 0x40 = +64
-            const unsigned long long lo = (s_tab[half & 0xff] & 0x8080808080808080ull) ^ 0xc0c0c0c0c0c0c0c0ull, hi = (s_tab[half >> 8] & 0x8080808080808080ull) ^ 0xc0c0c0c0c0c0c0c0ull;
-            B[t][kb] = nn_v4i{(int)(unsigned)lo, (int)(unsigned)(lo >> 32), (int)(unsigned)hi, (int)(unsigned)(hi >> 32)};
-        }
-    }
-    unsigned kbest[NNM_QT], ksec[NNM_QT];
-#pragma unroll
-    for (int t = 0; t < NNM_QT; t++) { kbest[t] = 0xffffffffu; ksec[t] = 0xffffffffu; }
-    const long long row0 = (long long)chunk * NN_CHUNK;
-    const int nrows = (int)min((long long)NN_CHUNK, ndb - row0);
-    const int ntiles = (nrows + 31) >> 5;
-    // staging role of this thread: row r of the tile, dword kb of that row
-    const int sr = tid & 31, skb = tid >> 5;
-    auto stage = [&](int tile, int buf) {
-        const int r = tile * 32 + sr;
-        const unsigned w = r < nrows ? db[(row0 + r) * 8 + skb] : 0u;
-        unsigned* d0 = s_a[buf] + ((skb * 2 + 0) * 32 + sr) * 4;        // bits 0..15 -> lane half 0
-        unsigned* d1 = s_a[buf] + ((skb * 2 + 1) * 32 + sr) * 4;        // bits 16..31 -> lane half 1
-        // (the same expansion by VALU arithmetic - n * 0x204081 & 0x01010101, * 0xfe, complement: 40 VALU per thread and tile - measured 8.3 against 7.9 ms)
-        const unsigned long long e0 = s_tab[w & 0xff], e1 = s_tab[(w >> 8) & 0xff], e2 = s_tab[(w >> 16) & 0xff], e3 = s_tab[w >> 24];
-        *reinterpret_cast<uint4*>(d0) = uint4{(unsigned)e0, (unsigned)(e0 >> 32), (unsigned)e1, (unsigned)(e1 >> 32)};
-        *reinterpret_cast<uint4*>(d1) = uint4{(unsigned)e2, (unsigned)(e2 >> 32), (unsigned)e3, (unsigned)(e3 >> 32)};
-    };
-    // C operand of a tile's first product: 256 * 64 + row-in-tile of D's register reg = (reg & 3) + 8 (reg >> 2) + 4 h (constant registers, shared by the query tiles)
-    nn_v16i cinit;
-#pragma unroll
-    for (int reg = 0; reg < 16; reg++) cinit[reg] = 256 * 64 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-    // best two of three keys in two instructions (v_min3 / v_med3), then (best, second) pairs merged in three
-    auto top2_of3 = [](unsigned a, unsigned b, unsigned c, unsigned& lo, unsigned& mid) { lo = min(min(a, b), c); mid = max(min(a, b), min(max(a, b), c)); };
-    auto merge2 = [](unsigned& b, unsigned& s2, unsigned ob, unsigned os) { s2 = min(min(s2, os), max(b, ob)); b = min(b, ob); };
-    // One tile of 32 DB rows against the wave's query tiles: products, then the (best, second) selection.  `ragged` (compile-time) = the chunk's
-    // last, partial tile, whose rows past the chunk get keys no real row beats.  (Measured in round 3, 2000 x 20 M: this form 7.8 ms; the same with
-    // the products of tile t issued before the selection of tile t-1 on a second accumulator set 10.0 ms - the wave's own matrix / VALU overlap
-    // costs more registers and scheduling freedom than the two resident workgroups already provide; four query tiles per wave 10.4 ms, spilling.)
-    auto products = [&](int tile, nn_v16i (&acc)[NNM_QT]) {
-        const int buf = tile & 1;
-        if (tile + 1 < ntiles) stage(tile + 1, buf ^ 1);
-#pragma unroll
-        for (int kb = 0; kb < 8; kb++) {
-            const nn_v4i A = *reinterpret_cast<const nn_v4i*>(s_a[buf] + ((kb * 2 + h) * 32 + j) * 4);     // lane (i = j, h): row i of the tile
-#pragma unroll
-            for (int t = 0; t < NNM_QT; t++) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A, B[t][kb], kb == 0 ? cinit : acc[t], 0, 0, 0);
-        }
-    };
-    auto select = [&](int tile, const nn_v16i (&acc)[NNM_QT], auto ragged) {
-        const unsigned tbase = (unsigned)tile * 32u;
-#pragma unroll
-        for (int t = 0; t < NNM_QT; t++) {
-            unsigned x[16];
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                x[reg] = (unsigned)acc[t][reg];                                                              // distance << 7 | row-in-tile
-                if (decltype(ragged)::value && tile * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h >= nrows) x[reg] = (511u << 7) + (unsigned)((reg & 3) + 8 * (reg >> 2) + 4 * h);   // distance 511: loses to every real row
-            }
-            unsigned b, s2;
-            top2_of3(x[0], x[1], x[2], b, s2);
-#pragma unroll
-            for (int g = 1; g < 5; g++) { unsigned lo, mid; top2_of3(x[3 * g], x[3 * g + 1], x[3 * g + 2], lo, mid); merge2(b, s2, lo, mid); }
-            merge2(b, s2, x[15], 0xffffffffu);
-            // tile key d << 7 | r  ->  chunk key d << 13 | (tile * 32 + r):  (k << 6) - 63 r + tile * 32  with r = k & 127 (bit 6 of r is clear)
-            const unsigned kb1 = (b << 6) - 63u * (b & 127u) + tbase, ks1 = (s2 << 6) - 63u * (s2 & 127u) + tbase;     // (both are real keys: 16 rows per lane)
-            merge2(kbest[t], ksec[t], kb1, ks1);
-        }
-    };
-    stage(0, 0);
-    __syncthreads();
-    const int nfull = nrows >> 5;                                      // whole tiles; tile nfull (if any) is the ragged one
-    nn_v16i acc[NNM_QT];
-    for (int tile = 0; tile < ntiles; tile++) {
-        products(tile, acc);
-        if (tile < nfull) select(tile, acc, std::false_type{}); else select(tile, acc, std::true_type{});
-        __syncthreads();
-    }
-    // ---- a query's rows were split over its two lanes (j, 0) and (j, 1): fold, then one partial per (query, chunk)
-#pragma unroll
-    for (int t = 0; t < NNM_QT; t++) {
-        const unsigned ob = (unsigned)__shfl_xor((int)kbest[t], 32), os = (unsigned)__shfl_xor((int)ksec[t], 32);
-        const unsigned b = min(kbest[t], ob), s2 = min(min(ksec[t], os), max(kbest[t], ob));
-        if (h == 0 && qidx[t] < nq) {
-            NNPart p;
-            p.best = (b >> 13) > 256u ? IMAX : (int)(b >> 13);                     // never-set keys and the ragged tile's filler rows carry a distance above 256
-            p.second = (s2 >> 13) > 256u ? IMAX : (int)(s2 >> 13);
-            p.idx = (b >> 13) > 256u ? -1 : row0 + (long long)(b & 0x1fffu) + base;
-            parts[(long long)qidx[t] * nchunks + chunk] = p;
-        }
-    }
-}
-
-// ---- the same scan on the FP4 matrix path (gfx950 only: v_mfma_scale_f32_32x32x64_f8f6f4, twice the i8 rate).  +-1 is exact in E2M1 (+1 = 0x2,
-// -1 = 0xA); the query side's block scale 2^6 (E8M0 133) gives the weight 64, so a product is -+64, the f32 accumulator holds integers below 2^16 -
-// exact - and with the same C operand 256 * 64 + row-in-tile a tile's accumulators are again its keys  distance << 7 | row-in-tile.  Positive floats
-// order like their bit patterns: the v_min3 / v_med3 tournament runs on the raw registers and only the two winners are converted.  A descriptor is 256
-// nibbles = 8 x 16 bytes: the expanded DB tile is 4 KB (the i8 form's is 8 KB) and a query tile costs 16 operand registers instead of 32, which is what
-// lets a wave keep QT = 3 or 4 query tiles (the i8 form spills at 4) and amortise the tile's expansion and operand reads over more queries.
 typedef int nn_v8i __attribute__((vector_size(32)));
 typedef float nn_v16f __attribute__((vector_size(64)));
-// Seeded scan (round 6): a query's FINAL second-best distance is at most the second-best distance over ANY subset of the rows; seed[q] carries that bound from
-// a first pass over the database's head (rows 0 .. 2^15).  A workgroup whose rows all lie BEHIND the head starts its skip threshold at the bound instead of at
-// "nothing seen yet": a tile can only matter if it holds a distance strictly below the bound (a row AT the bound loses the tie to the head's rows, which have
-// lower indices) - so the skip works from a chunk's first tile on (about one tile in sixteen survives instead of one in three).  chunk0 = index of this
-// launch's first chunk in rows / CH; part0, part_stride = where its partials go among all partials of the query (head sub-chunks first, then the rest).
-// EXP (round 6): `db` is the database EXPANDED in device memory (k_nn_expand: 128 B per row, 4 KB per tile of 32 rows in exactly the layout of the LDS tile),
-// so staging a tile is ONE 16-byte LDS-DMA per thread - no registers, no byte -> E2M1 table, no VALU - requested a whole superstep ahead.
-template <int QT, int OCC, int LCH, int TPB, int ABL = 0, bool EXP = false> __global__ __launch_bounds__(256, OCC) void k_hamming_nn_fp4(const unsigned* q, int nq, const unsigned* db, long long ndb, long long base, NNPart* parts, int nchunks,
-                                                                                                          const int* seed, int chunk0, int part0)
+// SEEDED SCAN.  A query's FINAL second-best distance is at most the second-best distance over ANY subset of the rows; seed[q] (nullptr: none) carries that
+// bound from a first pass over the database's head (rows 0 .. 2^15, k_hamming_seed).  A workgroup whose rows all lie BEHIND the head starts its threshold
+// at the bound instead of at "nothing seen yet": a tile can only matter if it holds a distance strictly below the bound (a row AT the bound loses the tie
+// to the head's rows, which have lower indices) - so the skip works from a chunk's first tile on.
+// EXP: `db` is the database EXPANDED in device memory (k_nn_expand: 128 B per row, 4 KB per tile of 32 rows in exactly the layout of the LDS tile), so
+// staging a tile is ONE 16-byte LDS-DMA per thread - no registers, no byte -> E2M1 table, no VALU - requested a whole superstep ahead.  Without it the
+// rows are loaded a superstep ahead and expanded through s_tab into LDS just before the barrier.
+// HAND-ORDERED SUPERSTEP.  Left to itself hipcc gathers the sixteen matrix instructions of a tile back to back, with the threshold tests and the tile's
+// operand reads (+ their lgkmcnt(0)) in front of them, so a wave's matrix pipe idles while it tests and waits.  Here a whole superstep of NN_FP4B_TPB tiles
+// is ONE asm statement whose text is generated (tools/gen_nn_fp4_block.py -> nn_fp4_block.inc): matrix instruction, two or three v_max3_f32 of a tile
+// finished long before, matrix instruction, ...; the next tile's operands are read a half tile ahead.  The statement owns its accumulators (registers it
+// clobbers), so nothing of a tile outlives it except ONE scalar: bit 8 t + u = tile u may matter to query tile t.  Those rare pairs are recomputed - four
+// matrix instructions - and folded in by compiled code behind the statement, while the superstep's tiles are still in LDS.  A threshold is therefore up
+// to one superstep stale: it only ever keeps more, never fewer.  Partial supersteps and the ragged tile take the compiled per-tile path.  hipcc must NOT
+// spill across the statement: a reload in front of it comes with `s_waitcnt vmcnt(0)`, i.e. waits for the prefetch issued just before - hence one
+// tile-operand set, the lane's LDS address and the scales made inside the statement, and addresses rebuilt at their (rare) uses instead of kept (check:
+// no scratch_ access between the loop's barriers).
+#include "nn_fp4_block.inc"
+#define NN_SHARE_EVERY 16                // supersteps between two reads of the shared bounds (a power of two)
+// SHARED BOUNDS.  `share` (nullptr: none) = two words per query: share[q] the smallest, share[nq + q] the second smallest distance among the head's best
+// pair (k_hamming_seed) and EVERY row any workgroup has found below its threshold since.  A row at distance d is OFFERED with two non-returning atomics,
+// atomicMin(best, d) and atomicMin(second, max(d, b)), b = the best as last read by the offering lane: b is the distance of some OTHER row, so max(d, b) is
+// at least the second smallest of two real rows - `second` never falls below the final second-best distance.  (The exact exchange
+// `old = atomicMin(best, d); atomicMin(second, max(old, d))` was built first: its returned value is a round trip of microseconds in front of the
+// workgroup's barrier and cost more than the bounds won.)  A tile whose distances all EXCEED some second best S holds neither the final best, nor the
+// final second best, nor a row tied with either - whichever rows S came from - so S + 1 is a threshold for everybody.  A workgroup re-reads the pair of
+// its queries every NN_SHARE_EVERY-th superstep by LDS-DMA with sc1 (device scope: a plain load is served from the reading XCD's L2, which the other
+// XCDs' atomics never reach), requested at a superstep's start and taken behind its barrier: the thresholds follow the best pair found ANYWHERE.  Under
+// the head's bound alone one (tile, query tile) in twenty-three is kept and recomputed, with the shared bounds one in five hundred.  The filter only
+// decides which tiles are looked at: the answers do not depend on the order the workgroups run in (tests/test_parity_match.py:
+// test_brute_force_nn_ties_across_chunks).
+template <int LCH, bool EXP> __global__ __launch_bounds__(256, 2) void k_hamming_nn_fp4b(const unsigned* q, int nq, const unsigned* db, long long ndb, long long base, NNPart* parts, int nchunks,
+                                                                                     const int* seed, int* share, long long rows0, int chrows, int part0)
 {
-    constexpr int ablate = ABL;                                        // measurement only (ORBHIP_NN_ABLATE): 1 = no threshold tests, 2 = no staging of new tiles; results are wrong
-    __shared__ unsigned s_tab[256];                                    // byte -> its 8 bits as FP4 nibbles (bit k -> nibble k): set = +1 (0x2), clear = -1 (0xA)
-    __shared__ __attribute__((aligned(16))) unsigned s_a[2][TPB * 8 * 32 * 4];   // TPB expanded DB tiles per workgroup barrier: [tile u][dword d of the row = 2 kb + h][row i] x 16 bytes, double-buffered
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), chunk = blockIdx.y + chunk0;
+    constexpr int QT = 4, TPB = NN_FP4B_TPB;
+    static_assert(TPB <= 8, "the keep mask has eight bits per query tile");
+    __shared__ unsigned s_tab[256];                                    // byte -> its 8 bits as E2M1 nibbles (bit k -> nibble k): set = +1 (0x2), clear = -1 (0xA)
+    __shared__ __attribute__((aligned(16))) unsigned s_a[2][TPB * 1024];   // the superstep's TPB tiles, double-buffered
+    __shared__ int s_bnd[4][2 * QT][64];                               // the queries' shared pairs as last read: [wave][t] the second best, [wave][QT + t] the best
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bx = blockIdx.x, by = blockIdx.y;
     {
         unsigned e = 0;
 #pragma unroll
@@ -238,312 +141,7 @@ template <int QT, int OCC, int LCH, int TPB, int ABL = 0, bool EXP = false> __gl
     __syncthreads();
     const int j = lane & 31, h = lane >> 5;
     constexpr int QG = 4 * QT * 32;
-    // ---- the wave's queries as B operands: lane (j, h), K block kb = dword 2 kb + h of query j, the SAME sign as the rows (set bit -> +1): a matching bit
-    // contributes +64, a differing one -64, and with C = 0 an accumulator is the similarity  sim = 64 (256 - 2 d) = 16384 - 128 d  of (row, query) - an
-    // integer of magnitude <= 2^14, exact in f32.  (Round 5 started the accumulators at 16384 + row so that they WERE the keys d << 7 | row: sixteen
-    // registers of constants that the second accumulator set below has no room for.  The keys are now made from the similarities only where a tile is kept.)
-    nn_v8i B[QT][4];
-    int qidx[QT];
-#pragma unroll
-    for (int t = 0; t < QT; t++) {
-        qidx[t] = blockIdx.x * QG + (wave * QT + t) * 32 + j;
-        const unsigned* qp = q + (long long)min(qidx[t], nq - 1) * 8;
-#pragma unroll
-        for (int kb = 0; kb < 4; kb++) {
-            const unsigned w = qp[2 * kb + h];
-            B[t][kb] = nn_v8i{(int)s_tab[w & 0xff], (int)s_tab[(w >> 8) & 0xff], (int)s_tab[(w >> 16) & 0xff], (int)s_tab[w >> 24], 0, 0, 0, 0};
-        }
-    }
-    // thr: a tile matters to a query only if it holds a similarity ABOVE it, i.e. a distance strictly below the running (or seeded) second best
-    unsigned kbest[QT], ksec[QT]; float thr[QT];
-#pragma unroll
-    for (int t = 0; t < QT; t++) {
-        kbest[t] = 0xffffffffu; ksec[t] = 0xffffffffu; thr[t] = -3.0e38f;
-        if (seed) { const int sd2 = seed[min(qidx[t], nq - 1)]; if (sd2 >= 0 && sd2 <= 256) thr[t] = (float)(16384 - 128 * sd2); }
-    }
-    constexpr int CH = 1 << LCH;                                      // DB rows per workgroup; chunk keys are distance << LCH | row-in-chunk
-    const long long row0 = (long long)chunk * CH;
-    const int nrows = (int)min((long long)CH, ndb - row0);
-    const int ntiles = (nrows + 31) >> 5;
-    const int sr = tid & 31, sd = tid >> 5;                            // staging role: row sr of the tile, dword sd of that row
-    // the next TPB tiles: loads issued first (they fly while the current tiles are worked on), expanded into LDS just before the barrier
-    unsigned wnext[TPB];
-    auto fetch = [&](int sup) {
-#pragma unroll
-        for (int u = 0; u < TPB; u++) { const int r = (sup * TPB + u) * 32 + sr; wnext[u] = r < nrows ? db[(row0 + r) * 8 + sd] : 0u; }
-    };
-    auto expand = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < TPB; u++) {
-            const unsigned w = wnext[u];
-            *reinterpret_cast<uint4*>(s_a[buf] + u * 1024 + (sd * 32 + sr) * 4) = uint4{s_tab[w & 0xff], s_tab[(w >> 8) & 0xff], s_tab[(w >> 16) & 0xff], s_tab[w >> 24]};
-        }
-    };
-    // EXP: the superstep's tiles by LDS-DMA, thread tid bytes [16 tid, 16 tid + 16) of each 4 KB tile (wave w: the tile's w-th KB)
-    auto stage_dma = [&](int sup, int buf) {
-#pragma unroll
-        for (int u = 0; u < TPB; u++) {
-            const int tile = sup * TPB + u;
-            if (tile < ntiles)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(db + ((row0 >> 5) + tile) * 1024 + tid * 4),
-                                                 (__attribute__((address_space(3))) void*)(s_a[buf] + u * 1024 + wave * 256), 16, 0, 0);
-        }
-    };
-    const nn_v16f czero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const float off_h = (float)(4 * h);
-    auto top2_of3 = [](unsigned a, unsigned b, unsigned c, unsigned& lo, unsigned& mid) { lo = min(min(a, b), c); mid = max(min(a, b), min(max(a, b), c)); };
-    auto merge2 = [](unsigned& b, unsigned& s2, unsigned ob, unsigned os) { s2 = min(min(s2, os), max(b, ob)); b = min(b, ob); };
-    auto products = [&](const unsigned* ta, nn_v16f (&acc)[QT]) {
-#pragma unroll
-        for (int kb = 0; kb < 4; kb++) {
-            const uint4 a4 = *reinterpret_cast<const uint4*>(ta + ((2 * kb + h) * 32 + j) * 4);               // lane (i = j, h): row i of the tile
-            const nn_v8i A = nn_v8i{(int)a4.x, (int)a4.y, (int)a4.z, (int)a4.w, 0, 0, 0, 0};
-#pragma unroll
-            for (int t = 0; t < QT; t++)      // (A, B, C, format of A = FP4, format of B = FP4, scale A: byte 0 of 127 = 2^0, scale B: byte 0 of 133 = 2^6)
-                acc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B[t][kb], kb == 0 ? czero : acc[t], 4, 4, 0, 127, 0, 133);
-        }
-    };
-    // the threshold test of one query tile: does ANY lane see a similarity above its threshold in this tile?  (eight v_max3_f32, a compare, a ballot)
-    auto test = [&](int t, const nn_v16f (&a)[QT]) -> bool {
-        const nn_v16f& x = a[t];
-        const float m0 = fmaxf(fmaxf(x[0], x[1]), x[2]), m1 = fmaxf(fmaxf(x[3], x[4]), x[5]), m2 = fmaxf(fmaxf(x[6], x[7]), x[8]), m3 = fmaxf(fmaxf(x[9], x[10]), x[11]), m4 = fmaxf(fmaxf(x[12], x[13]), x[14]);
-        const float mx = fmaxf(fmaxf(fmaxf(m0, m1), m2), fmaxf(fmaxf(m3, m4), x[15]));
-        return __ballot(mx > thr[t]) != 0;
-    };
-    // a kept (tile, query tile): keys d << 7 | row-in-tile = 16384 + row - sim as floats (positive floats order like their bits: the v_min3 / v_med3 tournament
-    // runs on the raw registers, only the two winners are converted), the two smallest merged into the chunk's running pair; `ragged`: rows past the end lose
-    auto tournament = [&](int tile, int t, const nn_v16f (&a)[QT], bool ragged) {
-        const unsigned tbase = (unsigned)tile * 32u;
-        unsigned x[16];
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const int rbase = (reg & 3) + 8 * (reg >> 2);
-            x[reg] = __float_as_uint(((float)(16384 + rbase) - a[t][reg]) + off_h);
-            if (ragged && tile * 32 + rbase + 4 * h >= nrows) x[reg] = __float_as_uint((float)((511 << 7) + rbase) + off_h);
-        }
-        unsigned b, s2;
-        top2_of3(x[0], x[1], x[2], b, s2);
-#pragma unroll
-        for (int g = 1; g < 5; g++) { unsigned lo, mid; top2_of3(x[3 * g], x[3 * g + 1], x[3 * g + 2], lo, mid); merge2(b, s2, lo, mid); }
-        merge2(b, s2, x[15], 0x7f7fffffu);                                                                  // (the largest finite float's bits: loses to every key)
-        const unsigned bi = (unsigned)__uint_as_float(b), si = (unsigned)__uint_as_float(s2);               // the two winners back to integers: d << 7 | r
-        const unsigned kb1 = ((bi >> 7) << LCH) + (bi & 127u) + tbase, ks1 = ((si >> 7) << LCH) + (si & 127u) + tbase;      // chunk keys d << LCH | (tile * 32 + r)
-        merge2(kbest[t], ksec[t], kb1, ks1);
-        // a later row at the running second best's own distance has a larger key than it (rows ascend): only a strictly smaller distance matters.
-        // (a never-set second best gives a threshold below every similarity; a seeded threshold is never lowered)
-        thr[t] = fmaxf(thr[t], 16384.0f - 128.0f * (float)(ksec[t] >> LCH));
-    };
-    if constexpr (EXP) { stage_dma(0, 0); __builtin_amdgcn_s_waitcnt(0x0f70); }      // (vmcnt(0))
-    else { fetch(0); expand(0); }
-    __syncthreads();
-    const int nfull = nrows >> 5, nsuper = (ntiles + TPB - 1) / TPB;
-    // ---- the tile loop.  A wave issues in order: with ONE accumulator set it runs the sixteen matrix instructions of a tile (512 cycles of the matrix pipe),
-    // then the threshold tests on their results - each pipe idle while the other works (0.44 of the matrix rate in round 5, two waves per SIMD).
-    // PIPELINED form (QT = 4, TPB a multiple of 3; round 6): the matrix instructions of tile i + 1 and the tests of tile i form one straight-line block, so the
-    // tests issue in the shadow of the matrix pipe.  A second full accumulator set does not fit beside the query operands (2 x 64 + 64 registers + the
-    // rest > 256 at two waves per SIMD: the first build spilled 260 loads per tile).  So the tile is handled as two HALVES of two query tiles and there are
-    // THREE register pairs: while the tests read the current tile's first half, the next tile's first half accumulates into the spare pair; the pair the
-    // tests just released takes the next tile's second half while the tests read the current second half.  The roles rotate with period three tiles,
-    // which is why TPB must be a multiple of 3 (all indices static after unrolling).  Inside a half the matrix instructions alternate between its two
-    // accumulators (consecutive instructions never share one: a filler between two instructions on the SAME accumulator costs ~40 cycles, MI355X_MICROARCH.md).
-    if constexpr (QT == 4 && TPB % 3 == 0) {
-        nn_v16f acc[6];
-        uint4 a4[4];
-        auto load_a = [&](const unsigned* ta) {
-#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
-            if constexpr (EXP) {
-                // spelled: while the NEXT superstep's LDS-DMA is in flight the compiler would put `s_waitcnt vmcnt(0)` in front of every ordinary LDS read
-                // (it has no address for the DMA's LDS side: orbhip_kernels_extract.hip, lds_read3_issue) - i.e. wait for the prefetch.  Lane (j, h) = lane l:
-                // its four operands are 1 KB apart from byte 16 l of the tile on
-                typedef int v4i_t __attribute__((vector_size(16)));
-                v4i_t q0, q1, q2, q3;
-                const unsigned addr = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)ta + 16u * (unsigned)lane;
-                asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
-                             : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3) : "v"(addr) : "memory");
-                a4[0] = uint4{(unsigned)q0[0], (unsigned)q0[1], (unsigned)q0[2], (unsigned)q0[3]}; a4[1] = uint4{(unsigned)q1[0], (unsigned)q1[1], (unsigned)q1[2], (unsigned)q1[3]};
-                a4[2] = uint4{(unsigned)q2[0], (unsigned)q2[1], (unsigned)q2[2], (unsigned)q2[3]}; a4[3] = uint4{(unsigned)q3[0], (unsigned)q3[1], (unsigned)q3[2], (unsigned)q3[3]};
-                return;
-            }
-#endif
-#pragma unroll
-            for (int kb = 0; kb < 4; kb++) a4[kb] = *reinterpret_cast<const uint4*>(ta + ((2 * kb + h) * 32 + j) * 4);
-        };
-        auto mm = [&](nn_v16f& d, int t, int kb) {
-            const nn_v8i A = nn_v8i{(int)a4[kb].x, (int)a4[kb].y, (int)a4[kb].z, (int)a4[kb].w, 0, 0, 0, 0};
-            d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B[t][kb], kb == 0 ? czero : d, 4, 4, 0, 127, 0, 133);
-        };
-        auto test1 = [&](int t, const nn_v16f& x) -> bool {
-            const float m0 = fmaxf(fmaxf(x[0], x[1]), x[2]), m1 = fmaxf(fmaxf(x[3], x[4]), x[5]), m2 = fmaxf(fmaxf(x[6], x[7]), x[8]), m3 = fmaxf(fmaxf(x[9], x[10]), x[11]), m4 = fmaxf(fmaxf(x[12], x[13]), x[14]);
-            const float mx = fmaxf(fmaxf(fmaxf(m0, m1), m2), fmaxf(fmaxf(m3, m4), x[15]));
-            return __ballot(mx > thr[t]) != 0;
-        };
-        auto tournament1 = [&](int tile, int t, const nn_v16f& a, bool ragged) {
-            const unsigned tbase = (unsigned)tile * 32u;
-            unsigned x[16];
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) {
-                const int rbase = (reg & 3) + 8 * (reg >> 2);
-                x[reg] = __float_as_uint(((float)(16384 + rbase) - a[reg]) + off_h);
-                if (ragged && tile * 32 + rbase + 4 * h >= nrows) x[reg] = __float_as_uint((float)((511 << 7) + rbase) + off_h);
-            }
-            unsigned b, s2;
-            top2_of3(x[0], x[1], x[2], b, s2);
-#pragma unroll
-            for (int g = 1; g < 5; g++) { unsigned lo, mid; top2_of3(x[3 * g], x[3 * g + 1], x[3 * g + 2], lo, mid); merge2(b, s2, lo, mid); }
-            merge2(b, s2, x[15], 0x7f7fffffu);
-            const unsigned bi = (unsigned)__uint_as_float(b), si = (unsigned)__uint_as_float(s2);
-            const unsigned kb1 = ((bi >> 7) << LCH) + (bi & 127u) + tbase, ks1 = ((si >> 7) << LCH) + (si & 127u) + tbase;
-            merge2(kbest[t], ksec[t], kb1, ks1);
-            thr[t] = fmaxf(thr[t], 16384.0f - 128.0f * (float)(ksec[t] >> LCH));
-        };
-        load_a(s_a[0]);                                                // tile 0: first half into pair 0, second half into pair 1
-#pragma unroll
-        for (int kb = 0; kb < 4; kb++) { mm(acc[0], 0, kb); mm(acc[1], 1, kb); }
-#pragma unroll
-        for (int kb = 0; kb < 4; kb++) { mm(acc[2], 2, kb); mm(acc[3], 3, kb); }
-        for (int sup = 0; sup < nsuper; sup++) {
-            const int buf = sup & 1;
-            if (sup + 1 < nsuper && !(ablate & 2)) { if constexpr (EXP) stage_dma(sup + 1, buf ^ 1); else fetch(sup + 1); }      // (EXP: everybody left that buffer at the barrier of the superstep before)
-#pragma unroll
-            for (int u = 0; u < TPB; u++) {
-                const int tile = sup * TPB + u;
-                if (tile >= ntiles) break;
-                const int cA = (3 - u % 3) % 3, cB = (cA + 1) % 3, sp = (cA + 2) % 3;             // static after unrolling: pair holding the current first half / second half / the spare
-                nn_v16f &x0 = acc[2 * cA], &x1 = acc[2 * cA + 1], &x2 = acc[2 * cB], &x3 = acc[2 * cB + 1], &n0 = acc[2 * sp], &n1 = acc[2 * sp + 1];
-                const bool last_of_super = u == TPB - 1;
-                if (last_of_super && sup + 1 < nsuper && !(ablate & 2)) {                            // the next tile lives in the other buffer: it is filled, everybody has left this one
-                    if constexpr (EXP) __builtin_amdgcn_s_waitcnt(0x0f70); else expand(buf ^ 1);
-                    __syncthreads();
-                }
-                const bool have_next = tile + 1 < ntiles;
-                const unsigned* tnext = last_of_super ? s_a[buf ^ 1] : s_a[buf] + (u + 1) * 1024;
-                if (tile < nfull) {
-                    unsigned keep = 0;
-                    if (have_next && (ablate & 1)) {                // (measurement only, ORBHIP_NN_ABLATE: the matrix instructions alone - results are wrong)
-                        load_a(tnext);
-                        if (ablate & 4) {                            // each accumulator's four instructions back to back
-                            mm(n0, 0, 0); mm(n0, 0, 1); mm(n0, 0, 2); mm(n0, 0, 3); mm(n1, 1, 0); mm(n1, 1, 1); mm(n1, 1, 2); mm(n1, 1, 3);
-                            mm(x0, 2, 0); mm(x0, 2, 1); mm(x0, 2, 2); mm(x0, 2, 3); mm(x1, 3, 0); mm(x1, 3, 1); mm(x1, 3, 2); mm(x1, 3, 3);
-                        } else {
-                            mm(n0, 0, 0); mm(n1, 1, 0); mm(n0, 0, 1); mm(n1, 1, 1); mm(n0, 0, 2); mm(n1, 1, 2); mm(n0, 0, 3); mm(n1, 1, 3);
-                            mm(x0, 2, 0); mm(x1, 3, 0); mm(x0, 2, 1); mm(x1, 3, 1); mm(x0, 2, 2); mm(x1, 3, 2); mm(x0, 2, 3); mm(x1, 3, 3);
-                        }
-                    } else if (have_next) {
-                        // Two straight-line blocks of eight matrix instructions and two tests each.  Left to itself the compiler issues the matrix
-                        // instructions of a block back to back and the tests behind them, and the two waves of a SIMD then fall into step - both queue
-                        // on the matrix pipe, both test while it idles: the tests cost their full 0.65 ms of 3.9 (profiles/r06_exp_config5_ablation.txt).
-                        // The group barriers spell the interleave out: one matrix instruction, three VALU instructions, eight times.
-                        load_a(tnext);
-                        mm(n0, 0, 0); mm(n1, 1, 0); mm(n0, 0, 1); mm(n1, 1, 1);
-                        keep |= test1(0, x0) ? 1u : 0u;
-                        mm(n0, 0, 2); mm(n1, 1, 2); mm(n0, 0, 3); mm(n1, 1, 3);
-                        keep |= test1(1, x1) ? 2u : 0u;
-                        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#pragma unroll
-                        for (int i = 0; i < 8; i++) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 3, 0); }
-                        if (keep & 1u) tournament1(tile, 0, x0, false);                             // (rare; the released pair is overwritten below)
-                        if (keep & 2u) tournament1(tile, 1, x1, false);
-                        mm(x0, 2, 0); mm(x1, 3, 0); mm(x0, 2, 1); mm(x1, 3, 1);
-                        keep |= test1(2, x2) ? 4u : 0u;
-                        mm(x0, 2, 2); mm(x1, 3, 2); mm(x0, 2, 3); mm(x1, 3, 3);
-                        keep |= test1(3, x3) ? 8u : 0u;
-#pragma unroll
-                        for (int i = 0; i < 8; i++) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 1); __builtin_amdgcn_sched_group_barrier(0x002, 3, 1); }
-                        if (keep & 4u) tournament1(tile, 2, x2, false);
-                        if (keep & 8u) tournament1(tile, 3, x3, false);
-                    } else {
-                        if (test1(0, x0)) tournament1(tile, 0, x0, false);
-                        if (test1(1, x1)) tournament1(tile, 1, x1, false);
-                        if (test1(2, x2)) tournament1(tile, 2, x2, false);
-                        if (test1(3, x3)) tournament1(tile, 3, x3, false);
-                    }
-                } else {                                               // the chunk's last, ragged tile (nothing follows it): every query tile, rows past the end lose
-                    tournament1(tile, 0, x0, true); tournament1(tile, 1, x1, true); tournament1(tile, 2, x2, true); tournament1(tile, 3, x3, true);
-                }
-            }
-        }
-    } else {
-        // one accumulator set: matrix instructions, then tests, then the kept tournaments (the experimental shapes of ORBHIP_NN=fp4:...)
-        nn_v16f acc[QT];
-        for (int sup = 0; sup < nsuper; sup++) {
-            const int buf = sup & 1;
-            if (sup + 1 < nsuper) fetch(sup + 1);
-#pragma unroll
-            for (int u = 0; u < TPB; u++) {
-                const int tile = sup * TPB + u;
-                if (tile >= ntiles) break;
-                products(s_a[buf] + u * 1024, acc);
-#pragma unroll
-                for (int t = 0; t < QT; t++) if (tile >= nfull || test(t, acc)) tournament(tile, t, acc, tile >= nfull);
-            }
-            if (sup + 1 < nsuper) expand(buf ^ 1);
-            __syncthreads();
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < QT; t++) {
-        const unsigned ob = (unsigned)__shfl_xor((int)kbest[t], 32), os = (unsigned)__shfl_xor((int)ksec[t], 32);
-        const unsigned b = min(kbest[t], ob), s2 = min(min(ksec[t], os), max(kbest[t], ob));
-        if (h == 0 && qidx[t] < nq) {
-            NNPart p;
-            p.best = (b >> LCH) > 256u ? IMAX : (int)(b >> LCH);
-            p.second = (s2 >> LCH) > 256u ? IMAX : (int)(s2 >> LCH);
-            p.idx = (b >> LCH) > 256u ? -1 : row0 + (long long)(b & (unsigned)(CH - 1)) + base;
-            parts[(long long)qidx[t] * nchunks + part0 + (int)blockIdx.y] = p;
-        }
-    }
-}
-// ---- the FP4 scan with the superstep's instruction order assigned by hand (k_hamming_nn_fp4b; the production form of the seeded scan).
-// k_hamming_nn_fp4 above is everything source order, scheduling barriers and priorities could get out of hipcc: the sixteen matrix instructions of a tile
-// come out back to back with the threshold tests and the tile's operand reads (+ their lgkmcnt(0)) in front of them, so a wave's matrix pipe idles while
-// it tests and waits (4.5 ms; this kernel: 3.7 on the expanded database, 4.2 on the bit form - profiles/r06_exp_config5_superstep.txt).  Here a whole superstep of NN_FP4B_TPB tiles is ONE asm statement whose text is
-// generated (tools/gen_nn_fp4_block.py -> nn_fp4_block.inc): matrix instruction, two or three v_max3_f32 of a tile finished long before, matrix
-// instruction, ...; the next tile's operands are read a half tile ahead.  The statement owns its accumulators (registers it clobbers), so nothing of a tile
-// outlives it except ONE scalar: bit 8 t + u = tile u may matter to query tile t.  Those rare pairs are recomputed - four matrix instructions - and folded
-// in by compiled code behind the statement, while the superstep's tiles are still in LDS.  A threshold is therefore up to one superstep stale: it only ever
-// keeps more, never fewer.  Partial supersteps and the ragged tile take the compiled per-tile path.  hipcc must NOT spill across the statement: a reload in
-// front of it comes with `s_waitcnt vmcnt(0)`, i.e. waits for the prefetch issued just before - hence one tile-operand set, the lane's LDS address and the
-// scales made inside the statement, and addresses rebuilt at their (rare) uses instead of kept (check: no scratch_ access between the loop's barriers).
-#include "nn_fp4_block.inc"
-#define NN_SHARE_EVERY 16                // supersteps between two reads of the shared bounds (a power of two)
-// SHARED BOUNDS.  `seed[q]` (nullptr: none) = the head's second-best distance: the head's rows precede every other row, so a later row AT that distance loses
-// the tie on the index and only a strictly smaller distance matters (as in k_hamming_nn_fp4).  `share` (nullptr: none) = two words per query: share[q] the
-// smallest, share[nq + q] the second smallest distance among the head's best pair (k_hamming_seed) and EVERY row any workgroup has found below its threshold
-// since.  A row at distance d is OFFERED with two non-returning atomics, atomicMin(best, d) and atomicMin(second, max(d, b)), b = the best as last read by
-// the offering lane: b is the distance of some OTHER row, so max(d, b) is at least the second smallest of two real rows - `second` never falls below the final
-// second-best distance.  (The exact exchange `old = atomicMin(best, d); atomicMin(second, max(old, d))` was built first: its returned value is a round trip of
-// microseconds in front of the workgroup's barrier and cost more than the bounds won.)  A tile whose distances all EXCEED some second best S holds neither
-// the final best, nor the final second best, nor a row tied with either - whichever rows S came from - so S + 1 is a threshold for everybody.  A workgroup
-// re-reads the pair of its queries every NN_SHARE_EVERY-th superstep by LDS-DMA with sc1 (device scope: a plain load is served from the reading XCD's L2, which
-// the other XCDs' atomics never reach), requested at a superstep's start and taken behind its barrier: the thresholds follow the best pair found ANYWHERE.
-// Under the head's bound alone one (tile, query tile) in twenty-three is kept and recomputed, with the shared bounds one in five hundred
-// (ORBHIP_NN_STATS=1; ORBHIP_NN_SHARE=0: without).  The filter only decides which tiles are looked at: the answers do not depend on the order the workgroups
-// run in (tests/test_parity_match.py: test_brute_force_nn_ties_across_chunks).
-// NW = wavefronts per workgroup: 4 (two workgroups per CU) or 8 (one: the same staged tiles serve 1024 queries instead of 512 - half the LDS-DMA requests and
-// bytes per matrix instruction; each half of the workgroup stages every other tile of a superstep).  The superstep's text does not depend on it.
-template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void k_hamming_nn_fp4b(const unsigned* q, int nq, const unsigned* db, long long ndb, long long base, NNPart* parts, int nchunks,
-                                                                                                        const int* seed, int* share, long long rows0, int chrows, int part0, int* stats, int share_mask)
-{
-    constexpr int QT = 4, TPB = NN_FP4B_TPB;
-    static_assert(TPB <= 8, "the keep mask has eight bits per query tile");
-    __shared__ unsigned s_tab[256];
-    __shared__ __attribute__((aligned(16))) unsigned s_a[2][TPB * 1024];
-    static_assert(NW == 4 || NW == 8, "four or eight wavefronts");
-    constexpr int NH = NW / 4;                                         // groups of 256 threads: group g stages tiles g, g + NH, ... of a superstep
-    static_assert(TPB % NH == 0, "every group stages the same number of tiles");
-    __shared__ int s_bnd[NW][2 * QT][64];                              // the queries' shared pairs as last read: [wave][t] the second best, [wave][QT + t] the best
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int bx = blockIdx.x, by = blockIdx.y;
-    if (tid < 256) {
-        unsigned e = 0;
-#pragma unroll
-        for (int t = 0; t < 8; t++) e |= (((tid >> t) & 1) ? 0x2u : 0xAu) << (4 * t);
-        s_tab[tid] = e;
-    }
-    __syncthreads();
-    const int j = lane & 31, h = lane >> 5;
-    constexpr int QG = NW * QT * 32;
-    nn_v4i B[QT][4];                                                   // (operand layout, signs and scales: k_hamming_nn_fp4)
+    nn_v4i B[QT][4];
     int qidx[QT];
 #pragma unroll
     for (int t = 0; t < QT; t++) {
@@ -581,26 +179,26 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
     const long long row0 = rows0 + (long long)by * chrows;
     const int nrows = (int)min((long long)chrows, ndb - row0);
     const int ntiles = (nrows + 31) >> 5;
-    const int sr = tid & 31, sd = (tid >> 5) & 7, grp = NH == 1 ? 0 : (wave >> 2), t256 = tid & 255;
-    unsigned wnext[TPB / NH];
+    const int sr = tid & 31, sd = tid >> 5;                            // staging role: row sr of the tile, dword sd of that row
+    unsigned wnext[TPB];
     auto fetch = [&](int sup) {
 #pragma unroll
-        for (int u2 = 0; u2 < TPB / NH; u2++) { const int r = (sup * TPB + u2 * NH + grp) * 32 + sr; wnext[u2] = r < nrows ? db[(row0 + r) * 8 + sd] : 0u; }
+        for (int u = 0; u < TPB; u++) { const int r = (sup * TPB + u) * 32 + sr; wnext[u] = r < nrows ? db[(row0 + r) * 8 + sd] : 0u; }
     };
     auto expand = [&](int buf) {
 #pragma unroll
-        for (int u2 = 0; u2 < TPB / NH; u2++) {
-            const unsigned w = wnext[u2];
-            *reinterpret_cast<uint4*>(s_a[buf] + (u2 * NH + grp) * 1024 + (sd * 32 + sr) * 4) = uint4{s_tab[w & 0xff], s_tab[(w >> 8) & 0xff], s_tab[(w >> 16) & 0xff], s_tab[w >> 24]};
+        for (int u = 0; u < TPB; u++) {
+            const unsigned w = wnext[u];
+            *reinterpret_cast<uint4*>(s_a[buf] + u * 1024 + (sd * 32 + sr) * 4) = uint4{s_tab[w & 0xff], s_tab[(w >> 8) & 0xff], s_tab[(w >> 16) & 0xff], s_tab[w >> 24]};
         }
     };
-    auto stage_dma = [&](int sup, int buf) {
+    auto stage_dma = [&](int sup, int buf) {                           // thread tid: bytes [16 tid, 16 tid + 16) of each 4 KB tile (wave w: the tile's w-th KB)
 #pragma unroll
-        for (int u2 = 0; u2 < TPB / NH; u2++) {
-            const int u = u2 * NH + grp, tile = sup * TPB + u;
+        for (int u = 0; u < TPB; u++) {
+            const int tile = sup * TPB + u;
             if (tile < ntiles)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(db + ((row0 >> 5) + tile) * 1024 + t256 * 4),
-                                                 (__attribute__((address_space(3))) void*)(s_a[buf] + u * 1024 + (wave & 3) * 256), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(db + ((row0 >> 5) + tile) * 1024 + tid * 4),
+                                                 (__attribute__((address_space(3))) void*)(s_a[buf] + u * 1024 + wave * 256), 16, 0, 0);
         }
     };
     const nn_v16f czero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -611,18 +209,20 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
     auto products1 = [&](const unsigned* ta, const nn_v4i (&b)[4]) -> nn_v16f {
         nn_v16f d = czero;
 #pragma unroll
-        for (int kb = 0; kb < 4; kb++) {
+        for (int kb = 0; kb < 4; kb++) {      // (A, B, C, format of A = FP4, format of B = FP4, scale A: byte 0 of 127 = 2^0, scale B: byte 0 of 133 = 2^6)
             const uint4 a4 = *reinterpret_cast<const uint4*>(ta + ((2 * kb + h) * 32 + j) * 4);
             d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(nn_v8i{(int)a4.x, (int)a4.y, (int)a4.z, (int)a4.w, 0, 0, 0, 0}, nn_v8i{b[kb][0], b[kb][1], b[kb][2], b[kb][3], 0, 0, 0, 0}, d, 4, 4, 0, 127, 0, 133);
         }
         return d;
     };
+    // the threshold test of one query tile: does ANY lane see a similarity above its threshold in this tile?  (eight v_max3_f32, a compare, a ballot)
     auto test1 = [&](int t, const nn_v16f& x) -> bool {
         const float m0 = fmaxf(fmaxf(x[0], x[1]), x[2]), m1 = fmaxf(fmaxf(x[3], x[4]), x[5]), m2 = fmaxf(fmaxf(x[6], x[7]), x[8]), m3 = fmaxf(fmaxf(x[9], x[10]), x[11]), m4 = fmaxf(fmaxf(x[12], x[13]), x[14]);
         const float mx = fmaxf(fmaxf(fmaxf(m0, m1), m2), fmaxf(fmaxf(m3, m4), x[15]));
         return __ballot(mx > thr[t]) != 0;
     };
-    auto tournament1 = [&](int tile, int t, const nn_v16f& a, bool ragged) {       // (keys, tournament, threshold: k_hamming_nn_fp4)
+    // a kept (tile, query tile): keys, tournament, the running pair and threshold (KEYS above); `ragged`: rows past the end get distance 511 and lose
+    auto tournament1 = [&](int tile, int t, const nn_v16f& a, bool ragged) {
         const unsigned tbase = (unsigned)tile * 32u;
         unsigned x[16];
 #pragma unroll
@@ -635,14 +235,11 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
         top2_of3(x[0], x[1], x[2], b, s2);
 #pragma unroll
         for (int g = 1; g < 5; g++) { unsigned lo, mid; top2_of3(x[3 * g], x[3 * g + 1], x[3 * g + 2], lo, mid); merge2(b, s2, lo, mid); }
-        merge2(b, s2, x[15], 0x7f7fffffu);
-        const unsigned bi = (unsigned)__uint_as_float(b), si = (unsigned)__uint_as_float(s2);
-        const unsigned kb1 = ((bi >> 7) << LCH) + (bi & 127u) + tbase, ks1 = ((si >> 7) << LCH) + (si & 127u) + tbase;
+        merge2(b, s2, x[15], 0x7f7fffffu);                                                                  // (the largest finite float's bits: loses to every key)
+        const unsigned bi = (unsigned)__uint_as_float(b), si = (unsigned)__uint_as_float(s2);               // the two winners back to integers: d << 7 | r
+        const unsigned kb1 = ((bi >> 7) << LCH) + (bi & 127u) + tbase, ks1 = ((si >> 7) << LCH) + (si & 127u) + tbase;      // chunk keys d << LCH | (tile * 32 + r)
         if (share && qidx[t] < nq) {
-            // this lane's two best rows of the tile, offered if they beat its threshold.  No atomic RETURNS anything (a returned value is a round trip of
-            // microseconds in front of the workgroup's barrier: the first build, with `old = atomicMin(best, d); atomicMin(second, max(old, d))`, lost more there
-            // than the bounds won): the loser of the exchange with the best is taken to be max(d, b) for b = the best AS LAST READ (or the tile's other row) - the
-            // distance of some OTHER row, so max(d, b) is at least the second smallest of two real rows: a valid, at worst slightly loose, offer to the second best
+            // this lane's two best rows of the tile, offered if they beat its threshold (SHARED BOUNDS above): b = the best AS LAST READ, or the tile's other row
             const int d1 = (int)(bi >> 7), d2 = (int)(si >> 7), bstar = s_bnd[wave][QT + t][lane];
             int qc = qidx[t];
             asm volatile("" : "+v"(qc));
@@ -650,6 +247,7 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
             if (d2 <= 256 && (float)(16384 - 128 * d2) > thr[t]) atomicMin(share + nq + qc, d2);                 // (the tile's other row is no farther)
         }
         merge2(kbest[t], ksec[t], kb1, ks1);
+        // (a never-set second best gives a threshold below every similarity; a seeded threshold is never lowered)
         thr[t] = fmaxf(thr[t], 16384.0f - 128.0f * (float)(ksec[t] >> LCH));
     };
     // one whole superstep: which (tile u, query tile t) hold a similarity above the query tile's threshold - bit 8 t + u
@@ -657,15 +255,12 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
 #if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
         unsigned keep, stmp;
         const unsigned addr = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)ta);
-#define NN_FP4B_ASM(BODY) asm volatile(BODY \
-                     : "=&s"(keep), "=&s"(stmp) \
-                     : "v"(B[0][0]), "v"(B[0][1]), "v"(B[0][2]), "v"(B[0][3]), "v"(B[1][0]), "v"(B[1][1]), "v"(B[1][2]), "v"(B[1][3]), \
-                       "v"(B[2][0]), "v"(B[2][1]), "v"(B[2][2]), "v"(B[2][3]), "v"(B[3][0]), "v"(B[3][1]), "v"(B[3][2]), "v"(B[3][3]), \
-                       "v"(thr[0]), "v"(thr[1]), "v"(thr[2]), "v"(thr[3]), "s"(addr) \
-                     : "memory", "vcc", "scc", NN_FP4B_CLOBBERS)
-        // (VAR != 0: measurement only - ORBHIP_NN_BLOCK_VAR, tools/gen_nn_fp4_block.py: the same superstep with parts of its text left out; wrong answers)
-        if constexpr ((VAR & 3) == 1) NN_FP4B_ASM(NN_FP4B_BODY1); else if constexpr ((VAR & 3) == 3) NN_FP4B_ASM(NN_FP4B_BODY3); else NN_FP4B_ASM(NN_FP4B_BODY);
-#undef NN_FP4B_ASM
+        asm volatile(NN_FP4B_BODY
+                     : "=&s"(keep), "=&s"(stmp)
+                     : "v"(B[0][0]), "v"(B[0][1]), "v"(B[0][2]), "v"(B[0][3]), "v"(B[1][0]), "v"(B[1][1]), "v"(B[1][2]), "v"(B[1][3]),
+                       "v"(B[2][0]), "v"(B[2][1]), "v"(B[2][2]), "v"(B[2][3]), "v"(B[3][0]), "v"(B[3][1]), "v"(B[3][2]), "v"(B[3][3]),
+                       "v"(thr[0]), "v"(thr[1]), "v"(thr[2]), "v"(thr[3]), "s"(addr)
+                     : "memory", "vcc", "scc", NN_FP4B_CLOBBERS);
         return keep;
 #else
         unsigned keep = 0;                                            // (the CPU emulation of the test suite: the same mask from the compiled pieces)
@@ -680,24 +275,18 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
     __syncthreads();
     if (bound) bounds_take();
     const int nfull = nrows >> 5, nsuper = (ntiles + TPB - 1) / TPB;
-    int nkept = 0;                                                     // (ORBHIP_NN_STATS: kept (tile, query tile) pairs of this wave)
     bool pending = false;
     for (int sup = 0; sup < nsuper; sup++) {
         const int buf = sup & 1, tile0 = sup * TPB;
         if (pending) bounds_take();                                                                         // (requested at the start of the superstep before, landed before its barrier)
         pending = false;
-        if constexpr (VAR >= 4) {                                                                           // (measurement only: no staging of new tiles, no barrier)
-            const unsigned keep = superstep(s_a[0]);
-            if (keep == 0x12345678u) tournament1(tile0, 0, products1(s_a[0], B[0]), false);
-            continue;
-        }
         if (sup + 1 < nsuper) { if constexpr (EXP) stage_dma(sup + 1, buf ^ 1); else fetch(sup + 1); }      // (everybody left that buffer at the barrier of the superstep before)
         // every NN_SHARE_EVERY-th superstep, the workgroups out of step with each other: the reads are device-scope (they go past the L2) and all workgroups of a
         // query group read the same few lines - once per superstep they queued on those lines' memory channel (5.1 ms against 3.3 for the scan without them)
-        if (bound && sup + 1 < nsuper && ((sup + by) & share_mask) == 0) { bounds_request(); pending = true; }
+        if (bound && sup + 1 < nsuper && ((sup + by) & (NN_SHARE_EVERY - 1)) == 0) { bounds_request(); pending = true; }
         if (tile0 + TPB <= nfull) {                                                                         // a superstep of whole tiles: the hand-ordered statement
             const unsigned keep = superstep(s_a[buf]);
-            nkept += __builtin_popcount(keep);
+            if (__builtin_expect(keep != 0, 0))                                                             // (rare: the hint keeps hipcc from spilling around the statement)
 #pragma unroll
             for (int t = 0; t < QT; t++) {
                 unsigned m = (keep >> (8 * t)) & 0xffu;
@@ -720,14 +309,13 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
         if (sup + 1 < nsuper) { if constexpr (!EXP) expand(buf ^ 1); __builtin_amdgcn_s_waitcnt(0x0f70); }      // (vmcnt(0): the next tiles and the bounds have landed)
         __syncthreads();
     }
-    if (stats && lane == 0) { atomicAdd(stats, nkept); atomicAdd(stats + 1, QT * min(ntiles, nfull)); }
 #pragma unroll
-    for (int t = 0; t < QT; t++) {
+    for (int t = 0; t < QT; t++) {      // a query's rows were split over its two lanes (j, 0) and (j, 1): fold, then one partial per (query, chunk)
         const unsigned ob = (unsigned)__shfl_xor((int)kbest[t], 32), os = (unsigned)__shfl_xor((int)ksec[t], 32);
         const unsigned b = min(kbest[t], ob), s2 = min(min(ksec[t], os), max(kbest[t], ob));
         if (h == 0 && qidx[t] < nq) {
             NNPart p;
-            p.best = (b >> LCH) > 256u ? IMAX : (int)(b >> LCH);
+            p.best = (b >> LCH) > 256u ? IMAX : (int)(b >> LCH);       // never-set keys and the ragged tile's filler rows carry a distance above 256
             p.second = (s2 >> LCH) > 256u ? IMAX : (int)(s2 >> LCH);
             p.idx = (b >> LCH) > 256u ? -1 : row0 + (long long)(b & (unsigned)(CH - 1)) + base;
             parts[(long long)qidx[t] * nchunks + part0 + by] = p;
@@ -735,7 +323,7 @@ template <int LCH, bool EXP, int VAR = 0, int NW = 4> __global__ __launch_bounds
     }
 }
 // The database as the FP4 scan reads it (orbhip_nn_expand_device): tile T = rows 32 T .. 32 T + 31 as 4 KB, [dword d of the row][row i] x 16 bytes = the eight
-// E2M1 nibbles of each of the dword's four bytes - byte for byte what k_hamming_nn_fp4's `expand` writes into LDS.  Rows past the end: zeros (never a winner:
+// E2M1 nibbles of each of the dword's four bytes - byte for byte what k_hamming_nn_fp4b's `expand` writes into LDS from the bit form.  Rows past the end: zeros (never a winner:
 // the scan's ragged tile masks them).  One thread per (tile, d, i).
 __global__ __launch_bounds__(256) void k_nn_expand(const unsigned* db, long long ndb, uint4* out, long long ntiles)
 {
@@ -806,134 +394,63 @@ __global__ __launch_bounds__(256) void k_hamming_merge(const NNPart* parts, int 
 
 bool orbhip_launch_hamming_nn(const uint8_t* d_q, int nq, const uint8_t* d_db, long long ndb, long long base,
                               long long* d_best_idx, int* d_best_dist, int* d_second, hipStream_t s, const uint8_t* d_dbx)
-{   // d_dbx: the same database expanded by orbhip_launch_nn_expand (nullptr: none) - taken by the default FP4 shape's seeded scan
+{   // d_dbx: the same database expanded by orbhip_launch_nn_expand (nullptr: none) - taken by the FP4 scan
     if (nq <= 0) return true;
     const int nchunks = (int)max(1LL, (ndb + NN_CHUNK - 1) / NN_CHUNK);
     NNPart* parts = (NNPart*)orbhip_nn_workspace(sizeof(NNPart) * (size_t)nq * nchunks, s);
     if (!parts) return false;                                    // the caller reports it: results would be left unwritten
-    // the matrix-core scan from a few chunks on (below that a call is latency, not throughput); ORBHIP_NN=valu (measurement only) keeps the popcount kernel
-    // ORBHIP_NN = valu | i8 | fp4[:<query tiles 2-4>[:<workgroups per CU 2-3>[:<log2 rows per workgroup 13|15|16>]]] (measurement only): the popcount kernel, the i8
-    // matrix-core scan, the FP4 one in the given shape
-    int form = ORBHIP_NN_DEFAULT, qt = ORBHIP_NN_FP4_QT, occ = ORBHIP_NN_FP4_OCC, lch = ORBHIP_NN_FP4_LCH, tpb = ORBHIP_NN_FP4_TPB;
-    if (const char* e = getenv("ORBHIP_NN")) {      // (read per call: a scan is at least a hundred microseconds; tests switch forms inside one process)
-        if (!strcmp(e, "valu")) form = 0; else if (!strcmp(e, "i8")) form = 1;
-        else if (!strncmp(e, "fp4", 3)) { form = 2; int a = 0, b2 = 0, c = 0, d = 0; const int k = sscanf(e + 3, ":%d:%d:%d:%d", &a, &b2, &c, &d); if (k >= 1) qt = a; if (k >= 2) occ = b2; if (k >= 3) lch = c; if (k >= 4) tpb = d; }
-        // a shape that was not compiled (the switch below lists them; all have >= 2^13 rows per workgroup, so their partials fit the workspace sized above):
-        // the default shape scans instead - said once on stderr - rather than a failure the callers could only report as "no device memory"
-        static const int known[] = {22131, 32131, 42131, 42151, 42152, 42154, 42158, 23154, 23151, 22154, 42134, 42164, 32154, 42156, 42153};
-        bool listed = false;
-        for (int v : known) listed = listed || v == qt * 10000 + occ * 1000 + lch * 10 + tpb;
-        if (form == 2 && !listed) {
-            static bool said = false;
-            if (!said) { said = true; fprintf(stderr, "orbhip: ORBHIP_NN=%s names a scan shape that is not built; the default fp4:%d:%d:%d:%d is used\n", e, ORBHIP_NN_FP4_QT, ORBHIP_NN_FP4_OCC, ORBHIP_NN_FP4_LCH, ORBHIP_NN_FP4_TPB); }
-            qt = ORBHIP_NN_FP4_QT; occ = ORBHIP_NN_FP4_OCC; lch = ORBHIP_NN_FP4_LCH; tpb = ORBHIP_NN_FP4_TPB;
-        }
+    // the matrix-core scan from a few chunks on (below that a call is latency, not throughput).  ORBHIP_NN=valu (measurement: tools/db_query_rate.py) keeps
+    // the popcount kernel at any size; any other value names no form: the default scans, said once on stderr.  (Read per call: a scan is at least a
+    // hundred microseconds, and tests switch forms inside one process.)
+    const char* e = getenv("ORBHIP_NN");
+    const bool valu = e && !strcmp(e, "valu");
+    if (e && *e && !valu) {
+        static bool said = false;
+        if (!said) { said = true; fprintf(stderr, "orbhip: ORBHIP_NN=%s names no scan form (valu is the only one); the default scan is used\n", e); }
     }
-    if (form >= 2 && ndb >= 4 * NN_CHUNK) {
-        const int qg = 4 * qt * 32, nch = (int)((ndb + ((long long)1 << lch) - 1) >> lch);      // (<= nchunks: the partials fit the workspace)
-        bool ok = true;
-#define NN_FP4(QT, OCC, LCH, TPB, GY, SEED, C0, P0, STRIDE) hipLaunchKernelGGL((k_hamming_nn_fp4<QT, OCC, LCH, TPB>), dim3((nq + qg - 1) / qg, GY, 1), dim3(256, 1, 1), 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_db, ndb, base, parts, STRIDE, SEED, C0, P0)
-        const int shape = qt * 10000 + occ * 1000 + lch * 10 + tpb;
-        // The seeded two-pass form for the default shape on databases of more than a few chunks (ORBHIP_NN_SEED=0: one pass, as in round 5): the head = the
-        // first 2^15 rows as 64 sub-chunks of 512 rows (256 workgroups, sixteen tiles each - a chunk of 2^15 rows takes ONE workgroup a millisecond), their
-        // merged second-best distance per query is the bound, the rest of the database is scanned under it.  Partials: [64 head sub-chunks][chunks 1 .. nch - 1].
-        const int ablate = getenv("ORBHIP_NN_ABLATE") ? atoi(getenv("ORBHIP_NN_ABLATE")) : 0;      // measurement only: 1 = no threshold tests, 2 = no staging of new tiles (wrong results)
-        const char* seed_env = getenv("ORBHIP_NN_SEED");                              // (read per call, like ORBHIP_NN: tests switch forms inside one process)
-        const bool seeded_default = !(seed_env && seed_env[0] == '0');
-        if (seeded_default && shape == 42156 && nch >= 2) {
-            // ROWS PER WORKGROUP of the main pass.  Every workgroup does the same work, so a launch runs in rounds of (2 x CUs) workgroups: 609 chunks of 2^15
-            // rows x 4 query groups = 2436 workgroups on 512 slots took five rounds with the last one three quarters empty.  The rows behind the head are split
-            // into the number of chunks that fills a whole number of rounds instead (a multiple of 256 rows, at most 2^15, at least 2048: a short database is
-            // spread over the chip instead of scanned by a handful of workgroups).  ORBHIP_NN_BLOCK=0 and the ablations keep chunks of 2^15 rows.
-            const char* blk_env0 = getenv("ORBHIP_NN_BLOCK");
-            const bool balanced = !(blk_env0 && blk_env0[0] == '0') && !getenv("ORBHIP_NN_ABLATE") && !(getenv("ORBHIP_NN_BALANCE") && getenv("ORBHIP_NN_BALANCE")[0] == '0');
-            // ORBHIP_NN_WAVES=8 (measurement): the main pass with eight wavefronts per workgroup, one workgroup per CU, 1024 queries per staged tile
-            const char* blk_env1 = getenv("ORBHIP_NN_BLOCK");
-            const bool waves8 = getenv("ORBHIP_NN_WAVES") && atoi(getenv("ORBHIP_NN_WAVES")) == 8 && !(blk_env1 && blk_env1[0] == '0') && !getenv("ORBHIP_NN_ABLATE") && !getenv("ORBHIP_NN_BLOCK_VAR");
-            const int qgm = waves8 ? 2 * qg : qg;                                  // queries per workgroup of the main pass
-            int chrows = 1 << 15, nmain = nch - 1;
-            if (balanced) {
-                static int ncu_of[64];                                             // (a benign race: every writer stores the same value)
-                int dev = 0; (void)hipGetDevice(&dev); dev = std::min(std::max(dev, 0), 63);
-                if (!ncu_of[dev]) { hipDeviceProp_t pr; ncu_of[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess ? std::max(1, pr.multiProcessorCount) : 256; }
-                const long long M = ndb - ((long long)1 << 15), nqg = (nq + qgm - 1) / qgm, slots = (waves8 ? 1LL : 2LL) * ncu_of[dev];
-                const long long rounds = std::max(1LL, (M * nqg + 32768LL * slots - 1) / (32768LL * slots));
-                const long long want = std::max(1LL, rounds * slots / nqg);
-                long long cr = ((M + want - 1) / want + 255) / 256 * 256;
-                cr = std::min(32768LL, std::max(2048LL, cr));
-                chrows = (int)cr; nmain = (int)((M + cr - 1) / cr);
-            }
-            const int nhead = 64, stride = nhead + nmain;
-            NNPart* p2 = (NNPart*)orbhip_nn_workspace(sizeof(NNPart) * (size_t)nq * stride + sizeof(int) * ((size_t)nq * 3 + 2), s);
-            if (!p2) return false;
-            parts = p2;
-            int* seed = reinterpret_cast<int*>(p2 + (size_t)nq * stride);
-            int* share = seed + nq;                                                // [nq] best, [nq] second best: k_hamming_nn_fp4b's shared bounds
-            int share_mask = NN_SHARE_EVERY - 1;                                   // ORBHIP_NN_SHARE_EVERY (measurement only): supersteps between two reads of the shared bounds, a power of two
-            if (const char* ev = getenv("ORBHIP_NN_SHARE_EVERY")) { const int v = atoi(ev); if (v >= 1 && (v & (v - 1)) == 0) share_mask = v - 1; }
-            int* stats = nullptr;                                                  // ORBHIP_NN_STATS=1 (measurement only): kept / examined (tile, query tile) pairs of the main pass on stderr
-            if (getenv("ORBHIP_NN_STATS")) stats = seed + 3 * (size_t)nq;
-            const long long ndb_all = ndb;
-            ndb = (long long)1 << 15;                                              // the head pass sees the first chunk only
-#define NN_FP4X(LCH, GY, SEED, C0, P0) hipLaunchKernelGGL((k_hamming_nn_fp4<4, 2, LCH, 6, 0, true>), dim3((nq + qg - 1) / qg, GY, 1), dim3(256, 1, 1), 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_dbx, ndb, base, parts, stride, SEED, C0, P0)
-#define NN_FP4B(LCH, EXP, DB, GY, SEED, SHARE, C0, CR, P0) hipLaunchKernelGGL((k_hamming_nn_fp4b<LCH, EXP>), dim3((nq + qg - 1) / qg, GY, 1), dim3(256, 1, 1), 0, s, (const unsigned*)d_q, nq, (const unsigned*)(DB), ndb, base, parts, stride, SEED, SHARE, C0, CR, P0, stats, share_mask)
-            // ORBHIP_NN_BLOCK=0 (measurement only): the compiler-scheduled tile loop of round 5 / 6 instead of the hand-ordered superstep
-            const char* blk_env = getenv("ORBHIP_NN_BLOCK");
-            const bool block = !(blk_env && blk_env[0] == '0') && ablate == 0;
-            if (block && d_dbx) NN_FP4B(9, true, d_dbx, nhead, (const int*)nullptr, (int*)nullptr, 0LL, 512, 0); else if (block) NN_FP4B(9, false, d_db, nhead, (const int*)nullptr, (int*)nullptr, 0LL, 512, 0);
-            else if (d_dbx) NN_FP4X(9, nhead, (const int*)nullptr, 0, 0); else NN_FP4(4, 2, 9, 6, nhead, (const int*)nullptr, 0, 0, stride);
-            ndb = ndb_all;
-            hipLaunchKernelGGL(k_hamming_seed, dim3((nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, (const NNPart*)parts, nq, stride, nhead, seed, share);
-            if (stats) (void)hipMemsetAsync(stats, 0, 2 * sizeof(int), s);      // (the head's own pairs are not counted)
-            const int bvar = getenv("ORBHIP_NN_BLOCK_VAR") ? atoi(getenv("ORBHIP_NN_BLOCK_VAR")) : 0;              // measurement only
-            const char* share_env = getenv("ORBHIP_NN_SHARE");                                                       // ORBHIP_NN_SHARE=0 (measurement only): the head's bound alone
-            int* const share_arg = share_env && share_env[0] == '0' ? (int*)nullptr : share;
-            if (block && d_dbx && (bvar == 1 || bvar == 3 || bvar == 4 || bvar == 5 || bvar == 7)) {
-#define NN_FP4BV(V) hipLaunchKernelGGL((k_hamming_nn_fp4b<15, true, V>), dim3((nq + qg - 1) / qg, nmain, 1), dim3(256, 1, 1), 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_dbx, ndb, base, parts, stride, (const int*)seed, share_arg, 32768LL, chrows, nhead, stats, share_mask)
-                if (bvar == 1) NN_FP4BV(1); else if (bvar == 3) NN_FP4BV(3); else if (bvar == 4) NN_FP4BV(4); else if (bvar == 5) NN_FP4BV(5); else NN_FP4BV(7);
-#undef NN_FP4BV
-            }
-            else if (block && waves8) {
-#define NN_FP4B8(EXP, DB) hipLaunchKernelGGL((k_hamming_nn_fp4b<15, EXP, 0, 8>), dim3((nq + qgm - 1) / qgm, nmain, 1), dim3(512, 1, 1), 0, s, (const unsigned*)d_q, nq, (const unsigned*)(DB), ndb, base, parts, stride, (const int*)seed, share_arg, 32768LL, chrows, nhead, stats, share_mask)
-                if (d_dbx) NN_FP4B8(true, d_dbx); else NN_FP4B8(false, d_db);
-#undef NN_FP4B8
-            }
-            else if (block && d_dbx) NN_FP4B(15, true, d_dbx, nmain, (const int*)seed, share_arg, 32768LL, chrows, nhead); else if (block) NN_FP4B(15, false, d_db, nmain, (const int*)seed, share_arg, 32768LL, chrows, nhead);
-            else if (ablate == 0 && d_dbx) NN_FP4X(15, nch - 1, (const int*)seed, 1, nhead);
-#undef NN_FP4X
-#undef NN_FP4B
-            else if (ablate == 0) NN_FP4(4, 2, 15, 6, nch - 1, (const int*)seed, 1, nhead, stride);
-            else {          // the same launch with parts of the loop compiled out: where the time goes (profiles/r06_exp_config5_ablation.txt)
-#define NN_FP4_ABL(A) hipLaunchKernelGGL((k_hamming_nn_fp4<4, 2, 15, 6, A>), dim3((nq + qg - 1) / qg, nch - 1, 1), dim3(256, 1, 1), 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_db, ndb, base, parts, stride, (const int*)seed, 1, nhead)
-                if (ablate == 1) NN_FP4_ABL(1); else if (ablate == 2) NN_FP4_ABL(2); else if (ablate == 7) NN_FP4_ABL(7); else NN_FP4_ABL(3);
-#undef NN_FP4_ABL
-            }
-            hipLaunchKernelGGL(k_hamming_merge, dim3((nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, (const NNPart*)parts, nq, stride, d_best_idx, d_best_dist, d_second);
-            if (stats) { int hst[2] = {0, 0}; (void)hipMemcpyAsync(hst, stats, sizeof(hst), hipMemcpyDeviceToHost, s); (void)hipStreamSynchronize(s); fprintf(stderr, "orbhip: FP4 scan kept %d of %d (tile, query tile) pairs\n", hst[0], hst[1]); }
-            return true;
-        }
-#define NN_FP4_PLAIN(QT, OCC, LCH, TPB) NN_FP4(QT, OCC, LCH, TPB, nch, (const int*)nullptr, 0, 0, nch)
-        switch (shape) {
-        case 22131: NN_FP4_PLAIN(2, 2, 13, 1); break; case 32131: NN_FP4_PLAIN(3, 2, 13, 1); break; case 42131: NN_FP4_PLAIN(4, 2, 13, 1); break;
-        case 42151: NN_FP4_PLAIN(4, 2, 15, 1); break; case 42152: NN_FP4_PLAIN(4, 2, 15, 2); break; case 42154: NN_FP4_PLAIN(4, 2, 15, 4); break; case 42158: NN_FP4_PLAIN(4, 2, 15, 8); break;
-        case 23154: NN_FP4_PLAIN(2, 3, 15, 4); break; case 23151: NN_FP4_PLAIN(2, 3, 15, 1); break; case 22154: NN_FP4_PLAIN(2, 2, 15, 4); break; case 42134: NN_FP4_PLAIN(4, 2, 13, 4); break;
-        case 42164: NN_FP4_PLAIN(4, 2, 16, 4); break; case 32154: NN_FP4_PLAIN(3, 2, 15, 4); break; case 42156: NN_FP4_PLAIN(4, 2, 15, 6); break; case 42153: NN_FP4_PLAIN(4, 2, 15, 3); break;
-        default: ok = false;
-        }
-#undef NN_FP4_PLAIN
-#undef NN_FP4
-        if (!ok) return false;
-        hipLaunchKernelGGL(k_hamming_merge, dim3((nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, (const NNPart*)parts, nq, nch, d_best_idx, d_best_dist, d_second);
-        return true;
-    } else if (form >= 1 && ndb >= 4 * NN_CHUNK) {
-        hipLaunchKernelGGL(k_hamming_nn_mfma, dim3((nq + NNM_QG - 1) / NNM_QG, nchunks, 1), dim3(256, 1, 1), 0, s, (const unsigned*)d_q, nq,
-                           (const unsigned*)d_db, ndb, base, parts, nchunks);
-    } else {
+    if (valu || ndb < 4 * NN_CHUNK) {
         const int qblocks = (nq + NN_T * NN_QPT - 1) / (NN_T * NN_QPT);
         hipLaunchKernelGGL(k_hamming_nn, dim3(qblocks, nchunks, 1), dim3(NN_T, 1, 1), 0, s, (const unsigned long long*)d_q, nq,
                            (const unsigned long long*)d_db, ndb, base, parts, nchunks);
+        hipLaunchKernelGGL(k_hamming_merge, dim3((nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, (const NNPart*)parts, nq, nchunks, d_best_idx, d_best_dist, d_second);
+        return true;
     }
-    hipLaunchKernelGGL(k_hamming_merge, dim3((nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, (const NNPart*)parts, nq, nchunks, d_best_idx, d_best_dist, d_second);
+    // The FP4 scan in two passes: the head = the first 2^15 rows as 64 sub-chunks of 512 rows (256 workgroups, sixteen tiles each - a chunk of 2^15 rows takes
+    // ONE workgroup a millisecond); behind it, if the database is longer, k_hamming_seed merges the head's second-best distance per query into the bound the
+    // main pass scans the rest of the database under.  Partials: [64 head sub-chunks][main chunks].
+    constexpr long long head = 1LL << 15;
+    const int qg = 4 * 4 * 32;                                   // queries per workgroup: four wavefronts of four query tiles
+    int chrows = 1 << 15, nmain = 0;
+    if (ndb > head) {
+        // ROWS PER WORKGROUP of the main pass.  Every workgroup does the same work, so a launch runs in rounds of (2 x CUs) workgroups: 609 chunks of 2^15
+        // rows x 4 query groups = 2436 workgroups on 512 slots took five rounds with the last one three quarters empty.  The rows behind the head are split
+        // into the number of chunks that fills a whole number of rounds instead (a multiple of 256 rows, at most 2^15, at least 2048: a short database is
+        // spread over the chip instead of scanned by a handful of workgroups).
+        static int ncu_of[64];                                             // (a benign race: every writer stores the same value)
+        int dev = 0; (void)hipGetDevice(&dev); dev = std::min(std::max(dev, 0), 63);
+        if (!ncu_of[dev]) { hipDeviceProp_t pr; ncu_of[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess ? std::max(1, pr.multiProcessorCount) : 256; }
+        const long long M = ndb - head, nqg = (nq + qg - 1) / qg, slots = 2LL * ncu_of[dev];
+        const long long rounds = std::max(1LL, (M * nqg + 32768LL * slots - 1) / (32768LL * slots));
+        const long long want = std::max(1LL, rounds * slots / nqg);
+        long long cr = ((M + want - 1) / want + 255) / 256 * 256;
+        cr = std::min(32768LL, std::max(2048LL, cr));
+        chrows = (int)cr; nmain = (int)((M + cr - 1) / cr);
+    }
+    const int nhead = 64, stride = nhead + nmain;
+    NNPart* p2 = (NNPart*)orbhip_nn_workspace(sizeof(NNPart) * (size_t)nq * stride + sizeof(int) * (size_t)nq * 3, s);
+    if (!p2) return false;
+    parts = p2;
+    int* seed = reinterpret_cast<int*>(p2 + (size_t)nq * stride);
+    int* share = seed + nq;                                                // [nq] best, [nq] second best: k_hamming_nn_fp4b's shared bounds
+    const dim3 grid_h((nq + qg - 1) / qg, nhead, 1), grid_m((nq + qg - 1) / qg, nmain, 1), block(256, 1, 1);
+    if (d_dbx) hipLaunchKernelGGL((k_hamming_nn_fp4b<9, true>), grid_h, block, 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_dbx, head, base, parts, stride, (const int*)nullptr, (int*)nullptr, 0LL, 512, 0);
+    else hipLaunchKernelGGL((k_hamming_nn_fp4b<9, false>), grid_h, block, 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_db, head, base, parts, stride, (const int*)nullptr, (int*)nullptr, 0LL, 512, 0);
+    if (nmain > 0) {
+        hipLaunchKernelGGL(k_hamming_seed, dim3((nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, (const NNPart*)parts, nq, stride, nhead, seed, share);
+        if (d_dbx) hipLaunchKernelGGL((k_hamming_nn_fp4b<15, true>), grid_m, block, 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_dbx, ndb, base, parts, stride, (const int*)seed, share, head, chrows, nhead);
+        else hipLaunchKernelGGL((k_hamming_nn_fp4b<15, false>), grid_m, block, 0, s, (const unsigned*)d_q, nq, (const unsigned*)d_db, ndb, base, parts, stride, (const int*)seed, share, head, chrows, nhead);
+    }
+    hipLaunchKernelGGL(k_hamming_merge, dim3((nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, (const NNPart*)parts, nq, stride, d_best_idx, d_best_dist, d_second);
     return true;
 }
 

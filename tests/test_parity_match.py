@@ -119,23 +119,20 @@ def test_brute_force_nn(backend, oracle):
     assert all(np.array_equal(a, b) for a, b in zip(merged, want))
 
 
+# i8 and the fp4:<shape> values selected scans that are no longer built: only valu is a form now, so each of them is a stray setting left in an
+# environment, and the default scan must answer (and say so on stderr) instead of a failed call or a different kernel
 @pytest.mark.parametrize("form", ["default", "i8", "fp4:2:2:13:1", "fp4:3:2:13:1", "fp4:4:2:15:4", "fp4:4:2:15:6:unseeded", "fp4:4:2:15:3", "fp4:2:3:15:4", "fp4:4:2:16:4", "fp4:4:2:15:8", "fp4:9:9:9:9", "valu"])
 def test_brute_force_nn_matrix_core_scan(backend, oracle, monkeypatch, form):
-    """Databases from four chunks (32 K rows) on are scanned on the matrix cores - k_hamming_nn_mfma (<+-1, +-1> = 256 - 2 Hamming as i8 products) or
-    k_hamming_nn_fp4 (the same as FP4 products on v_mfma_scale_f32_32x32x64_f8f6f4; query tiles per wave : workgroups per CU : log2 rows per workgroup); ORBHIP_NN picks the form:
+    """Databases from four chunks (32 K rows) on are scanned on the matrix cores - k_hamming_nn_fp4b (<+-1, +-1> = 256 - 2 Hamming as FP4 products on
+    v_mfma_scale_f32_32x32x64_f8f6f4); ORBHIP_NN=valu keeps the popcount kernel, any other value is ignored:
     ragged last tile and chunk, a query count that fills neither a tile nor a workgroup, planted exact matches, duplicated rows
-    (lowest index wins, second = best), an index base; every form against the oracle (the popcount kernel included)."""
-    # the default shape (fp4:4:2:15:6: four query tiles per wave, two workgroups per CU, 2^15 rows per workgroup, six tiles per barrier = the pipelined loop on
-    # three accumulator pairs) scans in two passes: the head's second-best distance per query seeds the skip threshold of every later chunk
-    # (ORBHIP_NN_SEED=0: one pass).  Both here: the duplicates of rows 100..104 in the last tile tie with the head's rows and must lose to them.
-    # fp4:9:9:9:9 is not a built shape: the default one scans (and says so on stderr) instead of a failed call
-    if form.endswith(":unseeded"):
-        form = form[:-len(":unseeded")]
-        monkeypatch.setenv("ORBHIP_NN_SEED", "0")
+    (lowest index wins, second = best), an index base; every setting against the oracle (the popcount kernel included)."""
+    # the scan runs in two passes: the head's second-best distance per query seeds the skip threshold of every later chunk.  The duplicates of rows
+    # 100..104 in the last tile tie with the head's rows and must lose to them.
     if form != "default":
         monkeypatch.setenv("ORBHIP_NN", form)
-    if backend.endswith("_emu.so") and form.startswith("fp4") and (form not in ("fp4:3:2:13:1",) or "ORBHIP_NN_SEED" in os.environ):
-        pytest.skip("the emulation's FP4 matrix product is slow: one FP4 form is enough here, all run on the GPU")
+    if backend.endswith("_emu.so") and form.startswith("fp4") and form != "fp4:3:2:13:1":
+        pytest.skip("the emulation's FP4 matrix product is slow: one retired value is enough here, all run on the GPU")
     rng = np.random.default_rng(5)
     n = 4 * 8192 + 1000 + 13 if backend.endswith("_emu.so") else 3 * 65536 + 8192 + 1000 + 13      # (several workgroups of the largest chunk on the GPU)
     db = rng.integers(0, 256, (n, 32), dtype=np.uint8)
@@ -152,19 +149,13 @@ def test_brute_force_nn_matrix_core_scan(backend, oracle, monkeypatch, form):
     assert np.array_equal(gb[0], want[0][:3].astype(np.int64) + 10 ** 10) and np.array_equal(gb[1], want[1][:3]) and np.array_equal(gb[2], want[2][:3])
 
 
-@pytest.mark.parametrize("waves", [4, 8])
-@pytest.mark.parametrize("expanded", [False, True])
-def test_brute_force_nn_ties_across_chunks(backend, oracle, expanded, waves, monkeypatch):
+@pytest.mark.parametrize("expanded", [False, True], ids=["False-4", "True-4"])      # (ids of the four-wave cases, from when an eight-wave form was built)
+def test_brute_force_nn_ties_across_chunks(backend, oracle, expanded):
     """The hand-ordered FP4 scan (k_hamming_nn_fp4b) skips a tile when none of its distances beats a bound - the head's second best (strict: the head's rows have
     the lowest indices) or the second best ANY workgroup has found so far + 1 (shared through device memory).  A database made of a few prototypes with a few
     flipped bits is nothing but ties: hundreds of rows at the best and at the second-best distance of every query, in every chunk, the lowest index among them
     often NOT in the head.  Best row (lowest index), best and second-best distance against the oracle, on the bit form and on the expanded database."""
     emu = backend.endswith("_emu.so")
-    if waves == 8:
-        # ORBHIP_NN_WAVES=8 (measurement form: eight wavefronts per workgroup on the same staged tiles, DESIGN.md section 9) must answer like the default
-        if emu:
-            pytest.skip("the eight-wave form runs on the GPU only (the emulation's FP4 product is slow; checked by hand: profiles/r06_exp_config5_eight_waves.txt)")
-        monkeypatch.setenv("ORBHIP_NN_WAVES", "8")
     rng = np.random.default_rng(21)
     n = 32768 + 8192 + 500 + 7 if emu else 5 * 32768 + 8192 + 500 + 7
     proto = rng.integers(0, 256, (6, 32), dtype=np.uint8)
@@ -193,6 +184,37 @@ def test_brute_force_nn_ties_across_chunks(backend, oracle, expanded, waves, mon
     for g, w in zip(got, want):
         assert np.array_equal(g, w)
     assert (got[1] == got[2]).sum() > nq // 3                                  # (the case is what it claims: best == second best for many queries)
+
+
+@pytest.mark.parametrize("n", [32768, 32769])
+def test_brute_force_nn_head_boundary(backend, oracle, n):
+    """The FP4 scan's head is the first 2^15 rows: a database of exactly 2^15 rows is the head pass alone (no seed, no main pass), one row more adds a main
+    pass of a single row.  Both sizes on the bit form and on the expanded database against the oracle, with exact matches and duplicated rows planted."""
+    emu = backend.endswith("_emu.so")
+    rng = np.random.default_rng(33)
+    db = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    nq = 70 if emu else 530
+    q = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+    q[:20] = db[rng.integers(0, n, 20)]; q[20:30] ^= 1
+    db[n - 3:] = db[7:10]; q[30:33] = db[7:10]                                # duplicates at the very end: index 7..9 must win, second == 0
+    want = oracle.bf_nn(q, db, fast=True)
+    D = orb_slam2_amd.DeviceBuffer
+    ddb, dq = D.from_array(db, library=backend), D.from_array(q, library=backend)
+    dx = D(orb_slam2_amd.nn_expanded_size(n, library=backend), library=backend)
+    orb_slam2_amd.nn_expand_device(None, ddb.ptr, n, dx.ptr, library=backend)
+    bi, bd, sd = D(nq * 8, library=backend), D(nq * 4, library=backend), D(nq * 4, library=backend)
+    for expanded in (False, True):
+        if expanded:
+            orb_slam2_amd.hamming_nn_device_expanded(None, dq.ptr, nq, ddb.ptr, dx.ptr, n, bi.ptr, bd.ptr, sd.ptr, library=backend)
+        else:
+            orb_slam2_amd.hamming_nn_device(None, dq.ptr, nq, ddb.ptr, n, bi.ptr, bd.ptr, sd.ptr, library=backend)
+        orb_slam2_amd.device_synchronize(library=backend)
+        got = bi.download((nq,), np.int64), bd.download((nq,), np.int32), sd.download((nq,), np.int32)
+        for g, w in zip(got, want):
+            assert np.array_equal(g, w), expanded
+        assert np.array_equal(got[0][30:33], np.arange(7, 10)) and np.all(got[1][30:33] == 0) and np.all(got[2][30:33] == 0)
+    for b in (ddb, dq, dx, bi, bd, sd):
+        b.free()
 
 
 def test_brute_force_nn_expanded_database(backend, oracle):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE.json config 5: brute-force 256-bit Hamming of a 2000-descriptor query frame against a keyframe descriptor DB
 resident in HBM (10 000 keyframes x 2000 descriptors = 640 MB).  Reports pair distances/s, the DB streaming rate, and the roofline of
-whichever kernel ran: the matrix-core scan (default from 32 K rows on: 512 i8 operations per pair against the dense i8 MFMA peak, ~5 POP/s
-spec, 4.4 measured - MI355X_MICROARCH.md) or, with ORBHIP_NN=valu, the popcount kernel against the integer-VALU issue peak
+whichever kernel ran: the FP4 matrix-core scan (default from 32 K rows on: 512 operations per pair against the dense FP4 MFMA rate, ~10 POP/s
+spec, 9.1 measured - MI355X_MICROARCH.md) or, with ORBHIP_NN=valu, the popcount kernel against the integer-VALU issue peak
 (8 v_xor_b32 @2 cycles + 8 v_bcnt_u32_b32 @4 cycles per 64 pairs and SIMD).  No framework: device memory through the library."""
 import json
 import os
@@ -51,19 +51,16 @@ for _ in range(reps):
 dt = (time.perf_counter() - t0) / reps
 pairs = NQ * NKF * PER
 peak_pairs = 1024 * 64 / (8 * 2 + 8 * 4) * 2.4e9
-assert os.environ.get("ORBHIP_NN_ABLATE", "0") != "0" or os.environ.get("ORBHIP_NN_BLOCK_VAR", "0") != "0" or int((bd.download((NQ,), np.int32) <= 4).sum()) == NQ      # (an ablated scan - measurement only - answers wrongly)
+assert int((bd.download((NQ,), np.int32) <= 4).sum()) == NQ
 valu = os.environ.get("ORBHIP_NN") == "valu"
-out = {"kernel": "k_hamming_nn (popcount)" if valu else ("k_hamming_nn_mfma" if os.environ.get("ORBHIP_NN") == "i8" else "k_hamming_nn_fp4"), "db_keyframes": NKF, "db_bytes": NKF * PER * 32, "query_ms": round(dt * 1e3, 2),
+out = {"kernel": "k_hamming_nn (popcount)" if valu else "k_hamming_nn_fp4b", "db_keyframes": NKF, "db_bytes": NKF * PER * 32, "query_ms": round(dt * 1e3, 2),
        "pair_distances_per_s": float(f"{pairs / dt:.4g}"), "db_stream_GBps": round(NKF * PER * 32 / dt / 1e9, 1), "queries_per_s_vs_full_db": round(NQ / dt, 1),
        "library": os.environ.get("ORBHIP_LIBRARY", "in-tree")}
 if valu:
     out["frac_of_int_valu_issue_peak"] = round(pairs / dt / peak_pairs, 3)
 else:
     out["matrix_TOPs"] = round(pairs * 512 / dt / 1e12, 1)
-    if out["kernel"] == "k_hamming_nn_fp4":
-        out["frac_of_fp4_mfma_rate_measured_9100_TOPs"] = round(pairs * 512 / dt / 9.1e15, 3); out["frac_of_fp4_mfma_spec_10000_TOPs"] = round(pairs * 512 / dt / 10e15, 3)
-    else:
-        out["frac_of_i8_mfma_peak_measured_4400_TOPs"] = round(pairs * 512 / dt / 4.4e15, 3); out["frac_of_i8_mfma_spec_5000_TOPs"] = round(pairs * 512 / dt / 5e15, 3)
+    out["frac_of_fp4_mfma_rate_measured_9100_TOPs"] = round(pairs * 512 / dt / 9.1e15, 3); out["frac_of_fp4_mfma_spec_10000_TOPs"] = round(pairs * 512 / dt / 10e15, 3)
 if EXPANDED:
     out["expanded_db_bytes"] = dx.nbytes; out["expand_once_ms"] = round(expand_ms, 2)
     # the same queries through the ordinary scan: the answers must be identical

@@ -45,11 +45,9 @@ def mfma(dst, aop, bop, first):
     return f"v_mfma_scale_f32_32x32x64_f8f6f4 {vr(dst, 16)}, {vr(aop, 4)}, {bop}, {c}, v{SCA}, v{SCB} op_sel_hi:[0,0,0] cbsz:4 blgp:4"
 
 
-def half_mfmas(s, one_operand_set=False):
+def half_mfmas(s):
     """the eight matrix instructions of half tile s: tile u = s // 2, query tiles 2 h and 2 h + 1, alternating accumulators"""
-    u, h = divmod(s, 2)
-    if one_operand_set:
-        u = 0
+    h = s % 2
     out = []
     for kb in range(4):
         for j in range(2):
@@ -87,17 +85,13 @@ def reads(u):
     return [read(u, kb) for kb in range(4)]
 
 
-def body(var):
-    """var 0: the production text.  Measurement only (ORBHIP_NN_BLOCK_VAR, wrong answers): 1 = no tests, 3 = matrix instructions alone (the first tile's
-    operands reused for every tile)"""
+def body():
     lines = ["s_mov_b32 %0, 0", f"v_mbcnt_lo_u32_b32 v{ADDR}, -1, 0", f"v_mbcnt_hi_u32_b32 v{ADDR}, -1, v{ADDR}", f"v_mov_b32_e32 v{SCA}, 0x7f", f"v_mov_b32_e32 v{SCB}, 0x85"]
     lines += [f"v_lshl_add_u32 v{ADDR}, v{ADDR}, 4, %22"] + reads(0)
     NH = 2 * TPB
     for s in range(NH + 2):
-        mm = half_mfmas(s, var == 3) if s < NH else []
+        mm = half_mfmas(s) if s < NH else []
         tt = half_tests(s - 2) if s >= 2 else []
-        if var in (1, 3):
-            tt = []
         u, h = divmod(s, 2)
         if not mm:
             for g in tt:
@@ -108,10 +102,10 @@ def body(var):
         for i, m in enumerate(mm):
             # operand kb = i // 2 of this tile: read behind the second-half matrix instruction 2 kb + 1 of the tile before (LDS returns in order: three, two,
             # one, no younger reads may still be out when operand 0, 1, 2, 3 is first used)
-            if h == 0 and i % 2 == 0 and (var != 3 or s == 0):
+            if h == 0 and i % 2 == 0:
                 lines.append(f"s_waitcnt lgkmcnt({(3 - i // 2) if s > 0 else 0})")
             lines.append(m)
-            if h == 1 and i % 2 == 1 and u + 1 < TPB and var != 3:
+            if h == 1 and i % 2 == 1 and u + 1 < TPB:
                 lines.append(read(u + 1, i // 2))
             upto = (n * (i + 1) + len(mm) - 1) // len(mm)
             for g in tt[done:upto]:
@@ -125,8 +119,6 @@ out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "orb_slam2_
 with open(out, "w") as f:
     f.write(f"// generated by tools/gen_nn_fp4_block.py {TPB} - the hand-ordered superstep of k_hamming_nn_fp4b; do not edit\n")
     f.write(f"#define NN_FP4B_TPB {TPB}\n#define NN_FP4B_V0 {V0}\n")
-    for var in (0, 1, 3):
-        lines = [".p2align 6"] + body(var)
-        f.write(f'#define NN_FP4B_BODY{var if var else ""} "' + "\\n\\t".join(lines) + '"\n')
+    f.write('#define NN_FP4B_BODY "' + "\\n\\t".join([".p2align 6"] + body()) + '"\n')
     f.write(f"#define NN_FP4B_CLOBBERS {clob}\n")
-print(out, len(body(0)), "instructions")
+print(out, len(body()), "instructions")
