@@ -78,6 +78,13 @@ public:
     // forward to this (Rcw / tcw / Ow = the frame's private mRcw / mtcw / mOw, which only the member itself can name).
     static bool IsInFrustum(Frame &F, const cv::Mat &Rcw, const cv::Mat &tcw, const cv::Mat &Ow, MapPoint* pMP, float viewingCosLimit);
 
+    // Which arithmetic the device uses for the members' scalar statements (projection, Fuse's chi-square gate, the epipolar line):
+    // 1 = the fused forms gcc emits under the reference's own flags (-march=native), 0 = one rounding per operation.  Default: 1 when this class's
+    // translation unit is compiled with FMA code generation (__FMA__), 0 otherwise; the environment variable ORBHIP_FP_CONTRACT=0|1 overrides.
+    // The batch functions of ORBmatcherBatch.h take the same default.
+    void SetFpContract(int mode);
+    int GetFpContract() const { return mbFpContract ? 1 : 0; }
+
     // The readers behind `friend class ORBmatcher;` in include/MapPoint.h (integration/apply_dropin.py adds that line): a map point's position, viewing
     // direction, scale-invariance range, mfMaxDistance and descriptor read in place under the point's own mutexes.  Defined in ORBmatcher.cc; declared here
     // because friendship reaches the class's members (this nested type is one), not the file's free functions.  No data member: the class layout is the reference's.
@@ -91,6 +98,7 @@ protected:
 
     float mfNNratio;            // best / second-best ratio
     bool mbCheckOrientation;    // rotation-consistency check on / off
+    bool mbFpContract;          // GetFpContract(); in the padding behind mbCheckOrientation: sizeof and every offset stay the reference's
 };
 
 } // namespace ORB_SLAM2

@@ -368,7 +368,9 @@ orbhip_status orbhip_search_by_bow(int device, int mode,
    octave), has_mp[i] = "GetMapPoint(i) != NULL" (such features are skipped), stereo[i] = "mvuRight[i] >= 0", the FeatureVector.
    F12 = the 3x3 fundamental matrix, row-major; (ex, ey) = the epipole the caller computes from the poses (:663-669);
    scale_factors2 / level_sigma2_2 = pKF2->mvScaleFactors / mvLevelSigma2 (nlevels2 entries).  match12[i1] = index in key frame 2
-   or -1 (vMatchedPairs = the pairs (i1, match12[i1]) in ascending i1); *nmatches = the return value.  Synchronous, host pointers. */
+   or -1 (vMatchedPairs = the pairs (i1, match12[i1]) in ascending i1); *nmatches = the return value.  Synchronous, host pointers.
+   check_ori | ORBHIP_FP_CONTRACT (here and in the batch form): the epipolar-line and epipole-distance statements in gcc's fused forms (see
+   ORBHIP_FP_CONTRACT below); without it every operation rounds once. */
 orbhip_status orbhip_search_for_triangulation(int device,
     const uint8_t* desc1, const float* kp1, const uint8_t* has_mp1, const uint8_t* stereo1, int n1,
     const uint32_t* fv1_node, const int32_t* fv1_off, const uint32_t* fv1_feat, int nfv1,
@@ -518,8 +520,19 @@ typedef enum {
     ORBHIP_PROJ_SIM3 = 5        /* :1154-1191  p3Dc1 = R*p3Dw+t; p3Dc2 = R2*p3Dc1+t2; z<0 -> skip; invz = 1.0/z; IsInImage; distance gate on norm(p3Dc2);
                                                PredictScale; radius = th*sf[level]; no viewing-angle gate */
 } orbhip_projection_kind;
+/* ORBHIP_FP_CONTRACT, OR-ed into orbhip_projection.kind: the member's scalar statements as gcc contracts them under the reference's own flags
+   (CMakeLists.txt:11-14: -O3 -march=native => -ffp-contract=fast), each form read off that build's object code:
+       u = fx*xc*invzc+cx   -> fma(fx*xc, invzc, cx)        LAST_FRAME, FRAME_KF (and v likewise)
+       u = fx*x+cx          -> fma(fx, x, cx)               KF_SIM3, FUSE, FUSE_SIM3, SIM3 (and v likewise)
+       ur = u-bf*invz       -> fma(-bf, invz, u)            LAST_FRAME, FUSE
+       Fuse's chi-square gate (chi2_gate): ex*ex+ey*ey -> fma(ex, ex, ey*ey); ex*ex+ey*ey+er*er -> fma(er, er, fma(ex, ex, ey*ey))
+   R*x+t, cv::norm and Mat::dot stay as above (cv::Mat arithmetic: H11).  Without the bit every operation rounds once, as before.  Every slot of one
+   batch / shared call that carries points must agree on the bit.  The two triangulation entries take the same bit in check_ori:
+       a = x1*F00+y1*F10+F20 -> fma(x1, F00, y1*F10) + F20;  b likewise;  c = x1*F02+y1*F12+F22 -> fma(y1, F12, x1*F02) + F22
+       num = a*x2+b*y2+c -> fma(b, y2, a*x2) + c;  den = a*a+b*b -> fma(a, a, b*b);  distex*distex+distey*distey -> fma(distex, distex, distey*distey) */
+#define ORBHIP_FP_CONTRACT 0x100
 typedef struct {
-    int32_t kind;               /* orbhip_projection_kind */
+    int32_t kind;               /* orbhip_projection_kind, optionally | ORBHIP_FP_CONTRACT; any other bit: ORBHIP_ERR_INVALID */
     int32_t gemm_mode;          /* how `R*x+t` rounds: 0 = products accumulated in double, rounded to float, then + t in float
                                    (cv::gemm's generic kernel; include/cvlite); 1 = OpenCV's small-matrix path: a0*b0 + a1*b1 + a2*b2 in float,
                                    then (float)((double)t0 + (double)c); 2 = not on the device: cam_x/y/z of every point hold the result of the

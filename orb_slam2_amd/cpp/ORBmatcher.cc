@@ -54,7 +54,21 @@ static int orbhip_default_device() { static const int d = getenv("ORBHIP_DEVICE"
 // failures are thrown like the extractor's (include/ORBextractor.h): never swallowed, never abort()
 static void orbhip_check(orbhip_status st, const char* who = "ORBmatcher") { if(st!=ORBHIP_OK) throw ORBhipError(std::string(who) + ": " + orbhip_last_error()); }
 
-ORBmatcher::ORBmatcher(float nnratio, bool checkOri) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}
+// The device arithmetic of the projection / Fuse / triangulation statements (include/orbhip.h, ORBHIP_FP_CONTRACT): gcc's fused forms when this
+// translation unit is compiled with FMA code generation (__FMA__, e.g. by the reference's -march=native) - the reference's ORBmatcher.cc, built with the same
+// flags, is contracted then - one rounding per operation otherwise.  ORBHIP_FP_CONTRACT=0|1 overrides (read per construction, like ORBextractor's).
+static bool orbhip_fp_contract_default()
+{
+#if defined(__FMA__)
+    bool fc = true;
+#else
+    bool fc = false;
+#endif
+    if (const char* e = getenv("ORBHIP_FP_CONTRACT")) fc = atoi(e) != 0;
+    return fc;
+}
+ORBmatcher::ORBmatcher(float nnratio, bool checkOri) : mfNNratio(nnratio), mbCheckOrientation(checkOri), mbFpContract(orbhip_fp_contract_default()) {}
+void ORBmatcher::SetFpContract(int mode) { mbFpContract = mode != 0; }
 
 int ORBmatcher::DescriptorDistance(const cv::Mat& a, const cv::Mat& b)
 {
@@ -256,10 +270,10 @@ static void orbhip_set_levels(orbhip_projection &P, const std::vector<float> &vS
     orbhip_level_table(logScaleFactor, nLevels, P.level_ratio);
 }
 static orbhip_projection orbhip_projection_of(int kind, const cv::Mat &R, const cv::Mat &t, const cv::Mat &Ow, float fx, float fy, float cx, float cy, float bf,
-                                              float minX, float minY, float maxX, float maxY, float th)
+                                              float minX, float minY, float maxX, float maxY, float th, bool fc)
 {
     orbhip_projection P; memset(&P, 0, sizeof P);
-    P.kind = kind; P.gemm_mode = orbhip_gemm_mode();
+    P.kind = kind | (fc ? ORBHIP_FP_CONTRACT : 0); P.gemm_mode = orbhip_gemm_mode();
     orbhip_set_pose(P, R, t);
     if(!Ow.empty()) for(int i=0;i<3;i++) P.Ow[i] = Ow.at<float>(i);
     P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.bf = bf;
@@ -441,7 +455,7 @@ int ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, 
     }
     G.done();
     orbhip_projection P = orbhip_projection_of(ORBHIP_PROJ_LAST_FRAME, Rcw, tcw, cv::Mat(), CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, CurrentFrame.mbf,
-                                               Frame::mnMinX, Frame::mnMinY, Frame::mnMaxX, Frame::mnMaxY, th);
+                                               Frame::mnMinX, Frame::mnMinY, Frame::mnMaxX, Frame::mnMaxY, th, mbFpContract);
     P.forward = bForward; P.backward = bBackward;
     orbhip_set_levels(P, CurrentFrame.mvScaleFactors, CurrentFrame.mnScaleLevels, CurrentFrame.mfLogScaleFactor);
     if(P.gemm_mode==2) orbhip_host_transform(G, Rcw, tcw);
@@ -467,7 +481,7 @@ int ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set
     }
     G.done();
     orbhip_projection P = orbhip_projection_of(ORBHIP_PROJ_FRAME_KF, Rcw, tcw, Ow, CurrentFrame.fx, CurrentFrame.fy, CurrentFrame.cx, CurrentFrame.cy, CurrentFrame.mbf,
-                                               Frame::mnMinX, Frame::mnMinY, Frame::mnMaxX, Frame::mnMaxY, th);
+                                               Frame::mnMinX, Frame::mnMinY, Frame::mnMaxX, Frame::mnMaxY, th, mbFpContract);
     orbhip_set_levels(P, CurrentFrame.mvScaleFactors, CurrentFrame.mnScaleLevels, CurrentFrame.mfLogScaleFactor);
     if(P.gemm_mode==2) orbhip_host_transform(G, Rcw, tcw);
     std::vector<unsigned char> blocked(CurrentFrame.N);
@@ -504,7 +518,7 @@ int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapP
     int nmatches=0;
     if(G.size()==0 || pKF->N==0) return 0;
     const orbhip_bounds bounds = orbhip_kf_bounds(pKF);
-    orbhip_projection P = orbhip_projection_of(ORBHIP_PROJ_KF_SIM3, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, bounds.min_x, bounds.min_y, bounds.max_x, bounds.max_y, (float)th);
+    orbhip_projection P = orbhip_projection_of(ORBHIP_PROJ_KF_SIM3, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, bounds.min_x, bounds.min_y, bounds.max_x, bounds.max_y, (float)th, mbFpContract);
     orbhip_set_levels(P, pKF->mvScaleFactors, pKF->mnScaleLevels, pKF->mfLogScaleFactor);
     if(P.gemm_mode==2) orbhip_host_transform(G, Rcw, tcw);
     std::vector<unsigned char> blocked(pKF->N); std::vector<int> fq(pKF->N);
@@ -528,7 +542,7 @@ struct OrbhipFuseJob
 // `shared`: the points read ONCE for every target of a FuseBatch (shared->index[k] = position in vpMapPoints; bad points are absent) - a target then copies
 // the records of the points it does not hold instead of visiting every map point again; NULL: read here (a single Fuse)
 // `sharedIn` (with `shared`): bit `t` of sharedIn[k] = shared point k is in target t (read in the same visit as the point), t = this job's number
-static void orbhip_fuse_collect(KeyFrame* pKF, const vector<MapPoint*> &vpMapPoints, const float th, OrbhipFuseJob &job, const OrbhipPoints* shared = NULL,
+static void orbhip_fuse_collect(KeyFrame* pKF, const vector<MapPoint*> &vpMapPoints, const float th, bool fc, OrbhipFuseJob &job, const OrbhipPoints* shared = NULL,
                                 const std::vector<unsigned long long>* sharedIn = NULL, int t = 0)
 {
     job.pKF = pKF;
@@ -536,7 +550,7 @@ static void orbhip_fuse_collect(KeyFrame* pKF, const vector<MapPoint*> &vpMapPoi
     cv::Mat tcw = pKF->GetTranslation();
     cv::Mat Ow = pKF->GetCameraCenter();
     const orbhip_bounds b = orbhip_kf_bounds(pKF);
-    job.P = orbhip_projection_of(ORBHIP_PROJ_FUSE, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, b.min_x, b.min_y, b.max_x, b.max_y, th);
+    job.P = orbhip_projection_of(ORBHIP_PROJ_FUSE, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, b.min_x, b.min_y, b.max_x, b.max_y, th, fc);
     orbhip_set_levels(job.P, pKF->mvScaleFactors, pKF->mnScaleLevels, pKF->mfLogScaleFactor);
     const int nMPs = vpMapPoints.size();
     job.G.reserve(shared ? shared->size() : nMPs);
@@ -637,7 +651,7 @@ static int orbhip_fuse_apply(OrbhipFuseJob &job, std::set<MapPoint*> *survivors,
 int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const float th)
 {
     OrbhipFuseJob job;
-    orbhip_fuse_collect(pKF, vpMapPoints, th, job);
+    orbhip_fuse_collect(pKF, vpMapPoints, th, mbFpContract, job);
     if(job.G.size()>0 && pKF->N>0)
     {
         orbhip_project_best_slot S = orbhip_fuse_slot(job);
@@ -648,6 +662,7 @@ int ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, const
 // LocalMapping::SearchInNeighbors (LocalMapping.cc:483-514): `for every target key frame: matcher.Fuse(pKFi, vpMapPointMatches)` as ONE device pass
 int FuseBatch(const std::vector<KeyFrame*> &vpTargetKFs, const std::vector<MapPoint*> &vpMapPoints, const float th)
 {
+    const bool fc = orbhip_fp_contract_default();          // what ORBmatcher's constructor would choose (no matcher object here)
     std::vector<OrbhipFuseJob> jobs(vpTargetKFs.size());
     std::vector<orbhip_project_best_slot> slots(vpTargetKFs.size());
     // every target is offered the same points: each is visited once (position, range, descriptor as they are before the loop - what an earlier target's
@@ -677,7 +692,7 @@ int FuseBatch(const std::vector<KeyFrame*> &vpTargetKFs, const std::vector<MapPo
             cv::Mat tcw = pKF->GetTranslation();
             cv::Mat Ow = pKF->GetCameraCenter();
             const orbhip_bounds b = orbhip_kf_bounds(pKF);
-            job.P = orbhip_projection_of(ORBHIP_PROJ_FUSE, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, b.min_x, b.min_y, b.max_x, b.max_y, th);
+            job.P = orbhip_projection_of(ORBHIP_PROJ_FUSE, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, pKF->mbf, b.min_x, b.min_y, b.max_x, b.max_y, th, fc);
             orbhip_set_levels(job.P, pKF->mvScaleFactors, pKF->mnScaleLevels, pKF->mfLogScaleFactor);
             job.bi.assign(shared.size(), -1); job.bd.assign(shared.size(), 256);
         }
@@ -692,7 +707,7 @@ int FuseBatch(const std::vector<KeyFrame*> &vpTargetKFs, const std::vector<MapPo
     else
     {
         for(size_t t=0; t<vpTargetKFs.size(); t++)
-            orbhip_fuse_collect(vpTargetKFs[t], vpMapPoints, th, jobs[t], &shared, bMasks ? &sharedIn : NULL, (int)t);
+            orbhip_fuse_collect(vpTargetKFs[t], vpMapPoints, th, fc, jobs[t], &shared, bMasks ? &sharedIn : NULL, (int)t);
         for(size_t t=0; t<vpTargetKFs.size(); t++) slots[t] = orbhip_fuse_slot(jobs[t]);      // (after every job exists: the slots point into them)
         if(!slots.empty())
             orbhip_check(orbhip_project_best_in_window_batch(orbhip_default_device(), (int)slots.size(), &slots[0], 1));
@@ -713,7 +728,7 @@ int ORBmatcher::Fuse(KeyFrame *pKF, cv::Mat Scw, const vector<MapPoint *> &vpPoi
 
     OrbhipFuseJob job; job.pKF = pKF;
     const orbhip_bounds b = orbhip_kf_bounds(pKF);
-    job.P = orbhip_projection_of(ORBHIP_PROJ_FUSE_SIM3, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, b.min_x, b.min_y, b.max_x, b.max_y, th);
+    job.P = orbhip_projection_of(ORBHIP_PROJ_FUSE_SIM3, Rcw, tcw, Ow, pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, b.min_x, b.min_y, b.max_x, b.max_y, th, mbFpContract);
     orbhip_set_levels(job.P, pKF->mvScaleFactors, pKF->mnScaleLevels, pKF->mfLogScaleFactor);
     const int nPoints = vpPoints.size();
     job.G.reserve(nPoints);
@@ -801,7 +816,7 @@ int ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &
         S.G.done();
         const orbhip_bounds b = orbhip_kf_bounds(S.target);
         // the intrinsics are key frame 1's in BOTH directions, as in the reference (:1105-1108)
-        S.P = orbhip_projection_of(ORBHIP_PROJ_SIM3, Rw, tw, cv::Mat(), pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy, 0.f, b.min_x, b.min_y, b.max_x, b.max_y, th);
+        S.P = orbhip_projection_of(ORBHIP_PROJ_SIM3, Rw, tw, cv::Mat(), pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy, 0.f, b.min_x, b.min_y, b.max_x, b.max_y, th, mbFpContract);
         for(int r=0;r<3;r++) { for(int c=0;c<3;c++) S.P.R2[3*r+c] = sR.at<float>(r,c); S.P.t2[r] = ts.at<float>(r); }
         orbhip_set_levels(S.P, S.target->mvScaleFactors, S.target->mnScaleLevels, S.target->mfLogScaleFactor);
         if(S.P.gemm_mode==2) orbhip_host_transform(S.G, Rw, tw, &sR, &ts);
@@ -978,7 +993,8 @@ int ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F
         const orbhip_tri_side &a = s1.s, &b = s2.s;
         orbhip_check(orbhip_search_for_triangulation(orbhip_default_device(), a.desc, a.kp, a.has_mp, a.stereo, a.n, a.fv_node, a.fv_off, a.fv_feat, a.nfv,
                                                      b.desc, b.kp, b.has_mp, b.stereo, b.n, b.fv_node, b.fv_off, b.fv_feat, b.nfv,
-                                                     F12flat, ex, ey, b.scale_factors, b.level_sigma2, b.nlevels, bOnlyStereo, mbCheckOrientation, &vMatches12[0], &nmatches));
+                                                     F12flat, ex, ey, b.scale_factors, b.level_sigma2, b.nlevels, bOnlyStereo,
+                                                     (mbCheckOrientation ? 1 : 0) | (mbFpContract ? ORBHIP_FP_CONTRACT : 0), &vMatches12[0], &nmatches));
     }
     vMatchedPairs.clear();
     vMatchedPairs.reserve(nmatches);
@@ -1008,7 +1024,7 @@ void SearchForTriangulationBatch(KeyFrame* pKF1, const std::vector<KeyFrame*> &v
         for(int r=0;r<3;r++) for(int c=0;c<3;c++) P.F12[3*r+c] = vF12[i].at<float>(r,c);
         orbhip_epipole(Cw, vpKF2[i], P.ex, P.ey);
     }
-    orbhip_check(orbhip_search_for_triangulation_batch(orbhip_default_device(), &s1.s, (int)nn, &pairs[0], bOnlyStereo, 0));
+    orbhip_check(orbhip_search_for_triangulation_batch(orbhip_default_device(), &s1.s, (int)nn, &pairs[0], bOnlyStereo, orbhip_fp_contract_default() ? ORBHIP_FP_CONTRACT : 0));
 }
 int TriangulationPairs(KeyFrame* pKF1, const std::vector<int> &vMatches12, std::vector<std::pair<size_t,size_t> > &vMatchedPairs)
 {

@@ -1483,8 +1483,12 @@ extern "C" orbhip_status orbhip_debug_candidates(orbhip_ctx* c, int frame, int l
 // ---------------------------------------------------------------------------------------------- projection-guided search
 static bool projection_ok(const orbhip_projection* P)
 {
-    return P && P->kind >= ORBHIP_PROJ_LAST_FRAME && P->kind <= ORBHIP_PROJ_SIM3 && P->gemm_mode >= 0 && P->gemm_mode <= 2 && P->nlevels >= 1 && P->nlevels <= ORBHIP_MAX_PROJ_LEVELS;
+    const int kind = P ? P->kind & ~ORBHIP_FP_CONTRACT : -1;          // the kind, optionally with the fused-arithmetic flag; any other bit is invalid
+    return P && kind >= ORBHIP_PROJ_LAST_FRAME && kind <= ORBHIP_PROJ_SIM3 && P->gemm_mode >= 0 && P->gemm_mode <= 2 && P->nlevels >= 1 && P->nlevels <= ORBHIP_MAX_PROJ_LEVELS;
 }
+// ORBHIP_FP_CONTRACT in proj->kind selects the fused kernels; the device copy carries the bare kind (the kernels compare it)
+static bool fp_contract_of(const orbhip_projection* P) { return P && (P->kind & ORBHIP_FP_CONTRACT); }
+static orbhip_projection bare_projection(const orbhip_projection& P) { orbhip_projection Q = P; Q.kind &= ~ORBHIP_FP_CONTRACT; return Q; }
 template <typename Query> static void gated_out(Query* q, int np) { if (q) for (int i = 0; i < np; i++) { memset(&q[i], 0, sizeof q[i]); q[i].radius = -1.0f; } }
 static void no_match(int32_t* best_idx, int32_t* best_dist, int nq) { for (int i = 0; i < nq; i++) { best_idx[i] = -1; best_dist[i] = 256; } }
 // a host input the kernels only read: laid out like Arena::io, its device copy handed back as a pointer to const
@@ -1520,6 +1524,22 @@ static orbhip_status frame_args(orbhip_ctx* c, int frame, int n, int use_u_right
     return ORBHIP_OK;
 }
 
+#ifdef ORBHIP_TEST_HOOKS
+// The CPU emulation build only: ORBHIP_TEST_RECORD=<file> appends every projected search (its inputs as the C ABI received them and its answers) to <file> -
+// how tests/golden/make_golden_native_matcher.py captures what the drop-in classes hand the device, for a replay through liborbhip.so.  A record: int32 tag
+// (1 = orbhip_project_search_*, 2 = one slot of orbhip_project_best_in_window_*), then length-prefixed (int64 bytes) arrays in a fixed order.
+static std::mutex g_record_mutex;
+struct TestRecord {
+    FILE* f = nullptr; std::unique_lock<std::mutex> lock;
+    explicit TestRecord(int tag) : lock(g_record_mutex) { const char* p = getenv("ORBHIP_TEST_RECORD"); if (p && *p && (f = fopen(p, "ab"))) fwrite(&tag, 4, 1, f); }
+    ~TestRecord() { if (f) fclose(f); }
+    template <typename T> void put(const T* a, size_t count) { if (!f) return; const long long b = a ? (long long)(count * sizeof(T)) : -1; fwrite(&b, 8, 1, f); if (a && count) fwrite(a, sizeof(T), count, f); }
+};
+#define ORBHIP_RECORD(...) do { __VA_ARGS__ } while (0)
+#else
+#define ORBHIP_RECORD(...) do { } while (0)
+#endif
+
 // queries given (P == nullptr) or derived on the device from map points under *P (orbhip_project_search_*): `queries` is then nullptr and nq = the point count
 static orbhip_status search_by_projection(const SearchFrame& F, const uint8_t* blocked, const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
                                           const orbhip_projection* P, const orbhip_map_point* points, orbhip_proj_query* queries_out,
@@ -1542,10 +1562,11 @@ static orbhip_status search_by_projection(const SearchFrame& F, const uint8_t* b
     float2* dgxy = nullptr; orbhip_proj_query* dq = nullptr; unsigned* dcand = nullptr; unsigned* dtop = nullptr;
     orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
     const int hn[2] = {n, 0}; int hres[2] = {0, 0};
+    const orbhip_projection hP = points ? bare_projection(*P) : orbhip_projection{};
     const hipError_t e = arena_call(F.device, s, [&](Arena& A) {
         if (F.on_host) { arena_in(A, &dk, F.kps, n); arena_in(A, &dd, F.desc, (size_t)n * 32); }
         A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32);
-        if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, P, 1); A.io(&dq, nq, (const orbhip_proj_query*)nullptr, 0, queries_out, queries_out ? nq : 0); }
+        if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, &hP, 1); A.io(&dq, nq, (const orbhip_proj_query*)nullptr, 0, queries_out, queries_out ? nq : 0); }
         else A.io(&dq, nq, queries, nq);
         if (F.on_host && F.u_right) arena_in(A, &dur, F.u_right, n);
         if (blocked) A.io(&dbl_in, n, blocked, n);
@@ -1564,10 +1585,15 @@ static orbhip_status search_by_projection(const SearchFrame& F, const uint8_t* b
         J.pts = dpts; J.proj = dP; J.q_out = dq;
         J.blocked_in = dbl_in; J.blocked_out = nullptr; J.feature_query = dfq; J.nmatches = dn + 1; J.events = dev;
         J.mode = mode; J.nnratio = nnratio; J.th_high = th_high; J.check_ori = check_ori; J.big_ws = dbig;
-        orbhip_launch_proj(J, s);
+        orbhip_launch_proj(J, s, fp_contract_of(P));
     });
     if (e != hipSuccess) return fail(ORBHIP_ERR_HIP, F.on_host ? "search_by_projection: %s" : "search_by_projection_frame: %s", hipGetErrorString(e));
     *nmatches = hres[1];
+    ORBHIP_RECORD(if (points) {
+        TestRecord R(1); const float par[2] = {nnratio, (float)0}; const int ipar[3] = {th_high, check_ori, hres[1]};
+        R.put(F.kps, n); R.put(F.desc, (size_t)n * 32); R.put(F.u_right, n); R.put(blocked, n); R.put(&F.bounds, 1); R.put(P, 1); R.put(points, nq); R.put(query_desc, (size_t)nq * 32);
+        R.put(par, 2); R.put(ipar, 3); R.put(feature_query, n);
+    });
     return ORBHIP_OK;
 }
 extern "C" orbhip_status orbhip_search_by_projection_bounds(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right,
@@ -1685,10 +1711,11 @@ static orbhip_status search_best_in_window(const SearchFrame& F, const float* in
     uint8_t* dqd = nullptr; float* dsg = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dbi = nullptr, *dbd = nullptr;
     float2* dgxy = nullptr; orbhip_best_query* dq = nullptr; orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
     const int hn[2] = {n, 0};
+    const orbhip_projection hP = points ? bare_projection(*P) : orbhip_projection{};
     const hipError_t e = arena_call(F.device, s, [&](Arena& A) {
         if (F.on_host) { arena_in(A, &dk, F.kps, n); arena_in(A, &dd, F.desc, (size_t)n * 32); }
         A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32); A.io(&dn, 8, hn, 2);
-        if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, P, 1); if (queries_out) A.io(&dq, nq, (const orbhip_best_query*)nullptr, 0, queries_out, nq); }
+        if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, &hP, 1); if (queries_out) A.io(&dq, nq, (const orbhip_best_query*)nullptr, 0, queries_out, nq); }
         else A.io(&dq, nq, queries, nq);
         if (F.on_host && F.u_right) arena_in(A, &dur, F.u_right, n);
         if (inv_level_sigma2 && nlevels > 0) A.io(&dsg, nlevels, inv_level_sigma2, nlevels);
@@ -1703,7 +1730,7 @@ static orbhip_status search_best_in_window(const SearchFrame& F, const float* in
         B.q = dq; B.qdesc = dqd; B.nq = nq; B.chi2_gate = chi2_gate; B.best_idx = dbi; B.best_dist = dbd;
         B.pts = dpts; B.proj = dP; B.q_out = points ? dq : nullptr;
         B.min_x = F.bounds.min_x; B.gw_inv = (float)ORBHIP_GRID_COLS / (float)(F.bounds.max_x - F.bounds.min_x);      // as orbhip_launch_match_grid lays the grid out
-        orbhip_launch_best_in_window(B, s);
+        orbhip_launch_best_in_window(B, s, fp_contract_of(P));
     });
     return e == hipSuccess ? ORBHIP_OK : fail(ORBHIP_ERR_HIP, F.on_host ? "search_best_in_window: %s" : "search_best_in_window_frame: %s", hipGetErrorString(e));
 }
@@ -1748,12 +1775,16 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
                 return fail(ORBHIP_ERR_INVALID, "slot %d does not name slot 0's points", s);
     }
     std::vector<int> live;
-    int cap = 1;
+    int cap = 1, fc = -1;                                    // fc: the slots' ORBHIP_FP_CONTRACT (one launch: every slot with points must agree)
     for (int s = 0; s < nslots; s++) {
         BestSlotIn& S = slots[s];
         if (S.n < 0 || S.nq < 0 || (S.nq > 0 && ((!S.queries && !S.points) || !S.query_desc || !S.best_idx || !S.best_dist)) || (S.n > 0 && (!S.kps || !S.desc)) ||
             !(S.bounds.max_x > S.bounds.min_x) || !(S.bounds.max_y > S.bounds.min_y) || (chi2_gate && (!S.inv_level_sigma2 || S.nlevels < 1)) || (S.nq > 0 && S.points && !projection_ok(S.proj)))
             return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
+        if (S.nq > 0 && S.points) {
+            if (fc >= 0 && fc != (int)fp_contract_of(S.proj)) return fail(ORBHIP_ERR_INVALID, "slot %d: the slots of one call mix ORBHIP_FP_CONTRACT and its absence", s);
+            fc = fp_contract_of(S.proj);
+        }
         no_match(S.best_idx, S.best_dist, S.nq);
         if (S.n == 0 || S.nq == 0) continue;
         live.push_back(s); cap = std::max(cap, S.n);
@@ -1774,6 +1805,8 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
     bool same_bounds = true;
     for (int k = 1; k < NL; k++) same_bounds = same_bounds && !memcmp(&slots[live[k]].bounds, &slots[live[0]].bounds, sizeof(orbhip_bounds));
     std::vector<BestParams> hB(NL); std::vector<int> pref(NL + 1, 0), hn(NL);
+    std::vector<orbhip_projection> hP(NL);                   // the slots' projections as the device reads them (bare kind)
+    for (int k = 0; k < NL; k++) if (slots[live[k]].points) hP[k] = bare_projection(*slots[live[k]].proj);
     for (int k = 0; k < NL; k++) { pref[k + 1] = pref[k] + (slots[live[k]].nq + 3) / 4; hn[k] = slots[live[k]].n; }
     BestParams* dB = nullptr; int *dpref = nullptr, *dn = nullptr, *dgs = nullptr, *dgi = nullptr; float2* dgxy = nullptr; orbhip_keypoint* dk0 = nullptr;
     uint8_t* dqd0 = nullptr; orbhip_map_point* dpts0 = nullptr; unsigned long long* dskip = nullptr;          // shared: the one copy of the points
@@ -1796,10 +1829,10 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
                     A.io(&dqd0, (size_t)S.nq * 32, S.query_desc, (size_t)S.nq * 32); A.io(&dpts0, S.nq, S.points, S.nq);
                     if (skip) A.io(&dskip, S.nq, reinterpret_cast<const unsigned long long*>(skip), S.nq);
                 }
-                dqd = dqd0; dpts = dpts0; A.io(&dP, 1, S.proj, 1);
+                dqd = dqd0; dpts = dpts0; A.io(&dP, 1, &hP[k], 1);
             } else {
                 A.io(&dqd, (size_t)S.nq * 32, S.query_desc, (size_t)S.nq * 32);
-                if (S.points) { A.io(&dpts, S.nq, S.points, S.nq); A.io(&dP, 1, S.proj, 1); }
+                if (S.points) { A.io(&dpts, S.nq, S.points, S.nq); A.io(&dP, 1, &hP[k], 1); }
                 else A.io(&dq, S.nq, S.queries, S.nq);
             }
             if (S.u_right) A.io(&dur, S.n, S.u_right, S.n);
@@ -1822,12 +1855,19 @@ static orbhip_status search_best_in_window_batch_impl(int device, int nslots, Be
         }
     }, [&] {
         for (int k = 0; k < (same_bounds ? 1 : NL); k++) launch_feature_grid(dk0, dn, cap, slots[live[k]].bounds, dgs, dgi, dgxy, same_bounds ? NL : 1, k, ts);
-        orbhip_launch_best_in_window_batch(dB, dpref, NL, pref[NL], ts);
+        orbhip_launch_best_in_window_batch(dB, dpref, NL, pref[NL], ts, fc == 1);
     });
     if (e != hipSuccess) {
         for (int k = 0; k < NL; k++) no_match(slots[live[k]].best_idx, slots[live[k]].best_dist, slots[live[k]].nq);
         return fail(ORBHIP_ERR_HIP, "search_best_in_window_batch: %s", hipGetErrorString(e));
     }
+    ORBHIP_RECORD(if (!shared) for (int k = 0; k < NL; k++) {
+        const BestSlotIn& S = slots[live[k]];
+        if (!S.points) continue;
+        TestRecord R(2); const int ipar[1] = {chi2_gate};
+        R.put(S.kps, S.n); R.put(S.desc, (size_t)S.n * 32); R.put(S.u_right, S.n); R.put(&S.bounds, 1); R.put(S.inv_level_sigma2, S.nlevels); R.put(S.proj, 1);
+        R.put(S.points, S.nq); R.put(S.query_desc, (size_t)S.nq * 32); R.put(ipar, 1); R.put(S.best_idx, S.nq); R.put(S.best_dist, S.nq);
+    });
     if (shared) {                                                                       // the slots stay where they are for orbhip_project_best_in_window_held
         g_held.device = device; g_held.floor = held_floor; g_held.B = hB; g_held.live_of_slot.assign((size_t)nslots, -1);
         for (int k = 0; k < NL; k++) g_held.live_of_slot[(size_t)live[k]] = k;
@@ -1852,13 +1892,14 @@ extern "C" orbhip_status orbhip_project_best_in_window_held(int device, int slot
     HIPCHK(hipSetDevice(device));
     hipStream_t ts = orbhip_thread_stream(device);
     uint8_t* dqd = nullptr; orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr; int *dbi = nullptr, *dbd = nullptr;
+    const orbhip_projection hP = bare_projection(*proj);
     const hipError_t e = arena_call(device, ts, [&](Arena& A) {
-        A.io(&dqd, (size_t)np * 32, point_desc, (size_t)np * 32); A.io(&dpts, np, points, np); A.io(&dP, 1, proj, 1);
+        A.io(&dqd, (size_t)np * 32, point_desc, (size_t)np * 32); A.io(&dpts, np, points, np); A.io(&dP, 1, &hP, 1);
         A.io(&dbi, np, (const int*)nullptr, 0, best_idx, np); A.io(&dbd, np, (const int*)nullptr, 0, best_dist, np);
     }, [&] {
         BestParams B = g_held.B[(size_t)k];
         B.q = nullptr; B.qdesc = dqd; B.nq = np; B.chi2_gate = chi2_gate; B.pts = dpts; B.proj = dP; B.q_out = nullptr; B.best_idx = dbi; B.best_dist = dbd; B.skip = nullptr; B.skip_bit = 0;
-        orbhip_launch_best_in_window(B, ts);
+        orbhip_launch_best_in_window(B, ts, fp_contract_of(proj));
     }, g_held.floor);
     if (e == hipErrorOutOfMemory) return fail(ORBHIP_ERR_INVALID, "the held scratch has no room for %d points", np);      // (the caller falls back to the full entry)
     if (e != hipSuccess) { no_match(best_idx, best_dist, np); return fail(ORBHIP_ERR_HIP, "project_best_in_window_held: %s", hipGetErrorString(e)); }

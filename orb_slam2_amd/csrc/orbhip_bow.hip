@@ -516,7 +516,25 @@ struct TriParams {
     float F[9]; float ex, ey; const float* scale2; const float* sigma2_2; int only_stereo;
 };
 
-__device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, int lane)
+// FC (ORBHIP_FP_CONTRACT, a template argument): the statements as gcc contracts them under the reference's own flags (-O3 -march=native), read off that
+// build's object code.  gcc picks the product it fuses per statement; for c it is the second one:
+//   a = x1*F00+y1*F10+F20        fma(x1, F00, y1*F10) + F20       (:143)
+//   b = x1*F01+y1*F11+F21        fma(x1, F01, y1*F11) + F21       (:144)
+//   c = x1*F02+y1*F12+F22        fma(y1, F12, x1*F02) + F22       (:145)
+//   num = a*x2+b*y2+c            fma(b, y2, a*x2) + c             (:147)
+//   den = a*a+b*b                fma(a, a, b*b)                   (:149)
+//   distex*distex+distey*distey  fma(distex, distex, distey*distey)   (:751)
+// (the epipole ex, ey is the caller's; num*num/den and the 3.84 sigma^2 bound have nothing to contract)
+template <bool FC> __device__ __forceinline__ float tri_line(float x1, float y1, float f0, float f1, float f2, bool second)
+{
+    if (!FC) return __fadd_rn(__fadd_rn(__fmul_rn(x1, f0), __fmul_rn(y1, f1)), f2);
+    return __fadd_rn(second ? __fmaf_rn(y1, f1, __fmul_rn(x1, f0)) : __fmaf_rn(x1, f0, __fmul_rn(y1, f1)), f2);
+}
+template <bool FC> __device__ __forceinline__ float tri_sum2(float a, float b, float c, float d)      // a*b+c*d with the first product fused
+{
+    return FC ? __fmaf_rn(a, b, __fmul_rn(c, d)) : __fadd_rn(__fmul_rn(a, b), __fmul_rn(c, d));
+}
+template <bool FC> __device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, int lane)
 {
     const BowMatchParams& P = T.M;
     if (a >= P.nf1) return;
@@ -538,7 +556,7 @@ __device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, 
                 x2[c] = T.kp2[4 * idx2[c]]; y2[c] = T.kp2[4 * idx2[c] + 1]; const int oct2 = (int)T.kp2[4 * idx2[c] + 3];
                 const uint4* d4 = reinterpret_cast<const uint4*>(P.d2 + (long long)idx2[c] * 32); da[c] = d4[0]; db[c] = d4[1];
                 const float dxe = __fsub_rn(T.ex, x2[c]), dye = __fsub_rn(T.ey, y2[c]);
-                near_epipole[c] = __fadd_rn(__fmul_rn(dxe, dxe), __fmul_rn(dye, dye)) < __fmul_rn(100.0f, T.scale2[oct2]);     // :747-753
+                near_epipole[c] = tri_sum2<FC>(dxe, dxe, dye, dye) < __fmul_rn(100.0f, T.scale2[oct2]);     // :747-753
                 chi2[c] = 3.84 * (double)T.sigma2_2[oct2];
             }
         }
@@ -557,10 +575,10 @@ __device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, 
                 const float qx1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x1), i)), qy1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y1), i));
                 const float qang = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ang1), i));
                 const int i1 = __builtin_amdgcn_readlane(idx1, i);
-                const float la = __fadd_rn(__fadd_rn(__fmul_rn(qx1, T.F[0]), __fmul_rn(qy1, T.F[3])), T.F[6]);      // epipolar line of kp1 in image 2 (:143-145)
-                const float lb = __fadd_rn(__fadd_rn(__fmul_rn(qx1, T.F[1]), __fmul_rn(qy1, T.F[4])), T.F[7]);
-                const float lc = __fadd_rn(__fadd_rn(__fmul_rn(qx1, T.F[2]), __fmul_rn(qy1, T.F[5])), T.F[8]);
-                const float den = __fadd_rn(__fmul_rn(la, la), __fmul_rn(lb, lb));
+                const float la = tri_line<FC>(qx1, qy1, T.F[0], T.F[3], T.F[6], false);      // epipolar line of kp1 in image 2 (:143-145)
+                const float lb = tri_line<FC>(qx1, qy1, T.F[1], T.F[4], T.F[7], false);
+                const float lc = tri_line<FC>(qx1, qy1, T.F[2], T.F[5], T.F[8], true);
+                const float den = tri_sum2<FC>(la, la, lb, lb);
                 const unsigned qx = __builtin_amdgcn_readlane((int)pa.x, i), qy = __builtin_amdgcn_readlane((int)pa.y, i), qz = __builtin_amdgcn_readlane((int)pa.z, i), qw = __builtin_amdgcn_readlane((int)pa.w, i);
                 const unsigned rx = __builtin_amdgcn_readlane((int)pb.x, i), ry = __builtin_amdgcn_readlane((int)pb.y, i), rz = __builtin_amdgcn_readlane((int)pb.z, i), rw = __builtin_amdgcn_readlane((int)pb.w, i);
                 int best = ORBHIP_TH_LOW, bidx = -1;
@@ -571,7 +589,7 @@ __device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, 
                                      __popc(rx ^ db[c].x) + __popc(ry ^ db[c].y) + __popc(rz ^ db[c].z) + __popc(rw ^ db[c].w);
                     bool ok = ok2[c] && dist <= ORBHIP_TH_LOW;                                   // :742
                     if (!stereo1 && !stereo2[c] && near_epipole[c]) ok = false;                  // :747-753
-                    const float num = __fadd_rn(__fadd_rn(__fmul_rn(la, x2[c]), __fmul_rn(lb, y2[c])), lc);
+                    const float num = __fadd_rn(tri_sum2<FC>(lb, y2[c], la, x2[c]), lc);
                     const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
                     if (den == 0.0f || !((double)dsqr < chi2[c])) ok = false;                    // :149-156
                     const int k1 = bm_wave_min(ok ? ((dist << 6) | (63 - lane)) : 0x7fffffff);      // `dist <= bestDist` keeps the LAST of equal candidates
@@ -601,10 +619,10 @@ __device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, 
         if (T.only_stereo && !stereo1) continue;
         const float x1 = T.kp1[4 * idx1], y1 = T.kp1[4 * idx1 + 1];
         // epipolar line of kp1 in image 2: l = x1' F12 = [a b c]  (:143-145), left-to-right sums like the reference's expression
-        const float la = __fadd_rn(__fadd_rn(__fmul_rn(x1, T.F[0]), __fmul_rn(y1, T.F[3])), T.F[6]);
-        const float lb = __fadd_rn(__fadd_rn(__fmul_rn(x1, T.F[1]), __fmul_rn(y1, T.F[4])), T.F[7]);
-        const float lc = __fadd_rn(__fadd_rn(__fmul_rn(x1, T.F[2]), __fmul_rn(y1, T.F[5])), T.F[8]);
-        const float den = __fadd_rn(__fmul_rn(la, la), __fmul_rn(lb, lb));
+        const float la = tri_line<FC>(x1, y1, T.F[0], T.F[3], T.F[6], false);
+        const float lb = tri_line<FC>(x1, y1, T.F[1], T.F[4], T.F[7], false);
+        const float lc = tri_line<FC>(x1, y1, T.F[2], T.F[5], T.F[8], true);
+        const float den = tri_sum2<FC>(la, la, lb, lb);
         const uint4* q4 = reinterpret_cast<const uint4*>(P.d1 + (long long)idx1 * 32);
         const uint4 qa = q4[0], qb = q4[1];
         int best = ORBHIP_TH_LOW, bidx = -1;
@@ -626,9 +644,9 @@ __device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, 
                     const float x2 = T.kp2[4 * idx2], y2 = T.kp2[4 * idx2 + 1]; const int oct2 = (int)T.kp2[4 * idx2 + 3];
                     if (!stereo1 && !stereo2) {                         // :747-753
                         const float dx = __fsub_rn(T.ex, x2), dy = __fsub_rn(T.ey, y2);
-                        if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.0f, T.scale2[oct2])) ok = false;
+                        if (tri_sum2<FC>(dx, dx, dy, dy) < __fmul_rn(100.0f, T.scale2[oct2])) ok = false;
                     }
-                    const float num = __fadd_rn(__fadd_rn(__fmul_rn(la, x2), __fmul_rn(lb, y2)), lc);
+                    const float num = __fadd_rn(tri_sum2<FC>(lb, y2, la, x2), lc);
                     const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
                     if (den == 0.0f || !((double)dsqr < 3.84 * (double)T.sigma2_2[oct2])) ok = false;      // :149-156
                 }
@@ -655,13 +673,23 @@ __device__ __forceinline__ void bow_triangulate_body(const TriParams& T, int a, 
 }
 __global__ __launch_bounds__(256) void k_bow_triangulate(TriParams T)
 {
-    bow_triangulate_body(T, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    bow_triangulate_body<false>(T, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
 }
 // one key frame against several neighbours in one launch (orbhip_search_for_triangulation_batch)
 __global__ __launch_bounds__(256) void k_bow_triangulate_batch(const TriParams* Ts, const int* pref, int npairs)
 {
     const int sl = bm_batch_slot(pref, npairs, blockIdx.x);
-    bow_triangulate_body(Ts[sl], (blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    bow_triangulate_body<false>(Ts[sl], (blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+}
+// the same two with the fused forms (ORBHIP_FP_CONTRACT): kernels of their own, so that the canonical ones' code is what it was
+__global__ __launch_bounds__(256) void k_bow_triangulate_fc(TriParams T)
+{
+    bow_triangulate_body<true>(T, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+}
+__global__ __launch_bounds__(256) void k_bow_triangulate_batch_fc(const TriParams* Ts, const int* pref, int npairs)
+{
+    const int sl = bm_batch_slot(pref, npairs, blockIdx.x);
+    bow_triangulate_body<true>(Ts[sl], (blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
 }
 __global__ __launch_bounds__(256) void k_bow_triangulate_finish_batch(const TriParams* Ts) { bow_finish_body(Ts[blockIdx.x].M, threadIdx.x); }
 
@@ -1088,14 +1116,15 @@ extern "C" orbhip_status orbhip_search_for_triangulation(int device,
     if (e == hipSuccess) {
         TriParams T; memset(&T, 0, sizeof T);
         BowMatchParams& P = T.M;
-        P.mode = 0; P.nnratio = 0.f; P.check_ori = check_ori;
+        P.mode = 0; P.nnratio = 0.f; P.check_ori = check_ori & ~ORBHIP_FP_CONTRACT;      // (the flag bit selects the fused kernel)
         P.d1 = d1; P.valid1 = h1; P.n1 = n1; P.fn1 = fn1; P.fo1 = fo1; P.ff1 = ff1; P.nf1 = nfv1;
         P.d2 = d2; P.valid2 = h2; P.n2 = n2; P.fn2 = fn2; P.fo2 = fo2; P.ff2 = ff2; P.nf2 = nfv2;
         P.match12 = m12; P.bin12 = bin12; P.hist = hist; P.nmatches = hist + ORBHIP_HISTO_LENGTH; P.overflow = P.nmatches + 1;
         T.kp1 = k1; T.kp2 = k2; T.st1 = s1; T.st2 = s2;
         for (int i = 0; i < 9; i++) T.F[i] = F12[i];
         T.ex = ex; T.ey = ey; T.scale2 = sc2; T.sigma2_2 = sg2; T.only_stereo = only_stereo;
-        hipLaunchKernelGGL(k_bow_triangulate, dim3((nfv1 + 3) / 4, 1, 1), dim3(256, 1, 1), 0, ts, T);
+        if (check_ori & ORBHIP_FP_CONTRACT) hipLaunchKernelGGL(k_bow_triangulate_fc, dim3((nfv1 + 3) / 4, 1, 1), dim3(256, 1, 1), 0, ts, T);
+        else hipLaunchKernelGGL(k_bow_triangulate, dim3((nfv1 + 3) / 4, 1, 1), dim3(256, 1, 1), 0, ts, T);
         hipLaunchKernelGGL(k_bow_match_finish, dim3(1, 1, 1), dim3(256, 1, 1), 0, ts, P);
         e = hipGetLastError();
     }
@@ -1238,7 +1267,7 @@ extern "C" orbhip_status orbhip_search_for_triangulation_batch(int device, const
     for (int k = 0; k < NL; k++) {
         const orbhip_tri_pair& Q = pairs[live[k]]; const Side2& S = B[k]; TriParams& T = hT[k]; memset(&T, 0, sizeof T);
         BowMatchParams& P = T.M;
-        P.mode = 0; P.nnratio = 0.f; P.check_ori = check_ori;
+        P.mode = 0; P.nnratio = 0.f; P.check_ori = check_ori & ~ORBHIP_FP_CONTRACT;      // (the flag bit selects the fused kernel)
         P.d1 = d1; P.valid1 = h1; P.n1 = n1; P.fn1 = fn1; P.fo1 = fo1; P.ff1 = ff1; P.nf1 = kf1->nfv;
         P.d2 = S.d; P.valid2 = S.h; P.n2 = Q.kf2->n; P.fn2 = S.fn; P.fo2 = S.fo; P.ff2 = S.ff; P.nf2 = Q.kf2->nfv;
         P.match12 = dm12[k]; P.bin12 = dbin[k]; P.hist = dhist[k]; P.nmatches = dhist[k] + ORBHIP_HISTO_LENGTH; P.overflow = P.nmatches + 1;
@@ -1248,7 +1277,8 @@ extern "C" orbhip_status orbhip_search_for_triangulation_batch(int device, const
     }
     hipError_t e = arena_upload(ts);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_bow_triangulate_batch, dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dT, (const int*)dpref, NL);
+        if (check_ori & ORBHIP_FP_CONTRACT) hipLaunchKernelGGL(k_bow_triangulate_batch_fc, dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dT, (const int*)dpref, NL);
+        else hipLaunchKernelGGL(k_bow_triangulate_batch, dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dT, (const int*)dpref, NL);
         hipLaunchKernelGGL(k_bow_triangulate_finish_batch, dim3(NL, 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dT);
         e = hipGetLastError();
     }

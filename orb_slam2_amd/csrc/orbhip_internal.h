@@ -153,7 +153,7 @@ struct ProjParams {         // projection-guided search core (ORBmatcher.cc:45-1
     int* big_ws;                // 4 n ints of device memory when the select kernel's per-feature tables do not fit LDS (orbhip_proj_select_big(n)); nullptr otherwise
 };
 bool orbhip_proj_select_big(int n);       // the per-feature tables of k_proj_select exceed the LDS budget: the caller provides ProjParams::big_ws
-void orbhip_launch_proj(const ProjParams& J, hipStream_t s);
+void orbhip_launch_proj(const ProjParams& J, hipStream_t s, bool fp_contract = false);      // fp_contract: the fused projection (ORBHIP_FP_CONTRACT)
 void orbhip_launch_proj_batch(const ProjParams* d_slots, int nslots, int max_nq, int max_n, float gwInv, float ghInv, hipStream_t s);
 struct BestParams {
     const orbhip_keypoint* kp; const uint8_t* desc; const float* u_right; const float* inv_level_sigma2;
@@ -164,8 +164,8 @@ struct BestParams {
     float min_x, gw_inv;        // left image bound and grid columns per pixel of the table's grid (gw_inv = 0: scan the whole table)
     const unsigned long long* skip; int skip_bit;     // (orbhip_project_best_in_window_shared) bit skip_bit of skip[iq] set: the query is not searched; nullptr: all are
 };
-void orbhip_launch_best_in_window(const BestParams& B, hipStream_t s);
-void orbhip_launch_best_in_window_batch(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s);
+void orbhip_launch_best_in_window(const BestParams& B, hipStream_t s, bool fp_contract = false);
+void orbhip_launch_best_in_window_batch(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s, bool fp_contract = false);
 size_t orbhip_proj_select_lds(int n);
 
 // kernel launchers (orbhip_kernels_extract.hip / orbhip_kernels_match.hip)

@@ -74,7 +74,13 @@ __device__ __forceinline__ int pj_predict_scale(const orbhip_projection& P, floa
     return level;
 }
 struct PjOut { float u, v, radius, ur; int level, min_level, max_level; };
-__device__ __forceinline__ bool pj_project(const orbhip_projection& P, const orbhip_map_point& m, PjOut& o)
+// FC (ORBHIP_FP_CONTRACT, a wave-uniform template argument): the member's statements as gcc contracts them under the reference's own flags (-O3 -march=native,
+// -ffp-contract=fast), read off that build's object code:
+//   fx*xc*invzc+cx                 fma(fx*xc, invzc, cx)          (:1367-1368, :1500-1501: the outer product is fused, fx*xc rounds)
+//   fx*x+cx                        fma(fx, x, cx)                 (:335-336, :863-864, :1023-1024, :1170-1171, :1250-1251)
+//   u-bf*invz                      fma(-bf, invz, u)              (:868, :1410: vfnmadd)
+// R*x+t, the distances and the dot product are cv::Mat arithmetic, not contracted by the caller's flags (H11): the same in both forms.
+template <bool FC> __device__ __forceinline__ bool pj_project(const orbhip_projection& P, const orbhip_map_point& m, PjOut& o)
 {
     const int kind = P.kind, gm = P.gemm_mode;
     float X, Y, Z;                                                     // the point in the frame the member projects from
@@ -90,8 +96,11 @@ __device__ __forceinline__ bool pj_project(const orbhip_projection& P, const orb
     if (kind == ORBHIP_PROJ_LAST_FRAME || kind == ORBHIP_PROJ_FRAME_KF) {
         invz = __double2float_rn(__ddiv_rn(1.0, (double)Z));         // const float invzc = 1.0/x3Dc.at<float>(2)  (:1362, :1498)
         if (kind == ORBHIP_PROJ_LAST_FRAME && invz < 0.0f) return false;                             // :1364-1365 (the relocalisation overload has no such test)
-        u = __fadd_rn(__fmul_rn(__fmul_rn(P.fx, X), invz), P.cx);     // CurrentFrame.fx*xc*invzc+CurrentFrame.cx  (:1367-1368, :1500-1501)
-        v = __fadd_rn(__fmul_rn(__fmul_rn(P.fy, Y), invz), P.cy);
+        if (FC) { u = __fmaf_rn(__fmul_rn(P.fx, X), invz, P.cx); v = __fmaf_rn(__fmul_rn(P.fy, Y), invz, P.cy); }
+        else {
+            u = __fadd_rn(__fmul_rn(__fmul_rn(P.fx, X), invz), P.cx); // CurrentFrame.fx*xc*invzc+CurrentFrame.cx  (:1367-1368, :1500-1501)
+            v = __fadd_rn(__fmul_rn(__fmul_rn(P.fy, Y), invz), P.cy);
+        }
         if (u < P.min_x || u > P.max_x) return false;                 // :1370-1373, :1503-1506
         if (v < P.min_y || v > P.max_y) return false;
     } else {
@@ -99,8 +108,8 @@ __device__ __forceinline__ bool pj_project(const orbhip_projection& P, const orb
         invz = (kind == ORBHIP_PROJ_KF_SIM3 || kind == ORBHIP_PROJ_FUSE) ? __fdiv_rn(1.0f, Z)          // 1/z  (:327, :860)
                                                                           : __double2float_rn(__ddiv_rn(1.0, (double)Z));      // 1.0/z  (:1015, :1174, :1254)
         const float x = __fmul_rn(X, invz), y = __fmul_rn(Y, invz);
-        u = __fadd_rn(__fmul_rn(P.fx, x), P.cx);                      // fx*x+cx
-        v = __fadd_rn(__fmul_rn(P.fy, y), P.cy);
+        if (FC) { u = __fmaf_rn(P.fx, x, P.cx); v = __fmaf_rn(P.fy, y, P.cy); }
+        else { u = __fadd_rn(__fmul_rn(P.fx, x), P.cx); v = __fadd_rn(__fmul_rn(P.fy, y), P.cy); }          // fx*x+cx
         if (!(u >= P.min_x && u < P.max_x && v >= P.min_y && v < P.max_y)) return false;                // KeyFrame::IsInImage (KeyFrame.cc:610-613)
     }
     o.u = u; o.v = v; o.ur = 0.0f;
@@ -111,7 +120,7 @@ __device__ __forceinline__ bool pj_project(const orbhip_projection& P, const orb
         if (P.forward) { o.min_level = oct; o.max_level = -1; }       // :1382-1387
         else if (P.backward) { o.min_level = 0; o.max_level = oct; }
         else { o.min_level = oct - 1; o.max_level = oct + 1; }
-        o.ur = __fsub_rn(u, __fmul_rn(P.bf, invz));                   // u - CurrentFrame.mbf*invzc (:1410)
+        o.ur = FC ? __fmaf_rn(-P.bf, invz, u) : __fsub_rn(u, __fmul_rn(P.bf, invz));                   // u - CurrentFrame.mbf*invzc (:1410)
         return true;
     }
     float dist;
@@ -127,11 +136,11 @@ __device__ __forceinline__ bool pj_project(const orbhip_projection& P, const orb
     o.level = level;
     o.radius = __fmul_rn(P.th, P.scale_factors[min(max(level, 0), ORBHIP_MAX_PROJ_LEVELS - 1)]);
     o.min_level = level - 1; o.max_level = kind == ORBHIP_PROJ_FRAME_KF ? level + 1 : level;          // :1524 / :364-366
-    if (kind == ORBHIP_PROJ_FUSE) o.ur = __fsub_rn(u, __fmul_rn(P.bf, invz));                       // const float ur = u-bf*invz (:868)
+    if (kind == ORBHIP_PROJ_FUSE) o.ur = FC ? __fmaf_rn(-P.bf, invz, u) : __fsub_rn(u, __fmul_rn(P.bf, invz));      // const float ur = u-bf*invz (:868)
     return true;
 }
 
-__device__ __forceinline__ void proj_candidates_body(const ProjParams& J, float gwInv, float ghInv)
+template <bool FC> __device__ __forceinline__ void proj_candidates_body(const ProjParams& J, float gwInv, float ghInv)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int iq = blockIdx.x * 4 + wave;
@@ -141,7 +150,7 @@ __device__ __forceinline__ void proj_candidates_body(const ProjParams& J, float 
     if (J.pts) {                                                       // the member's projection of map point iq (every lane the same arithmetic)
         const orbhip_map_point m = J.pts[iq];
         PjOut o;
-        live = pj_project(*J.proj, m, o);
+        live = pj_project<FC>(*J.proj, m, o);
         q.x = live ? o.u : 0.0f; q.y = live ? o.v : 0.0f; q.radius = live ? o.radius : -1.0f; q.ur = live ? o.ur : 0.0f;
         q.min_level = live ? o.min_level : 0; q.max_level = live ? o.max_level : 0; q.blocks = m.blocks; q.angle = m.angle;
         if (lane == 0) J.q_out[iq] = q;
@@ -222,9 +231,11 @@ __device__ __forceinline__ void proj_candidates_body(const ProjParams& J, float 
     if (lane < PJ_K) J.top[PJ_REC * iq + lane] = out;
     if (lane == PJ_K) J.top[PJ_REC * iq + PJ_K] = more ? 1u : 0u;
 }
-__global__ __launch_bounds__(256) void k_proj_candidates(ProjParams J, float gwInv, float ghInv) { proj_candidates_body(J, gwInv, ghInv); }
-// several frames (camera slots) per launch: blockIdx.y = slot, its parameters come from a table in device memory
-__global__ __launch_bounds__(256) void k_proj_candidates_batch(const ProjParams* Js, float gwInv, float ghInv) { const ProjParams J = Js[blockIdx.y]; proj_candidates_body(J, gwInv, ghInv); }
+__global__ __launch_bounds__(256) void k_proj_candidates(ProjParams J, float gwInv, float ghInv) { proj_candidates_body<false>(J, gwInv, ghInv); }
+// the same with the fused projection (ORBHIP_FP_CONTRACT): a kernel of its own, so that the canonical one's code is what it was
+__global__ __launch_bounds__(256) void k_proj_candidates_fc(ProjParams J, float gwInv, float ghInv) { proj_candidates_body<true>(J, gwInv, ghInv); }
+// several frames (camera slots) per launch: blockIdx.y = slot, its parameters come from a table in device memory (given queries: no projection)
+__global__ __launch_bounds__(256) void k_proj_candidates_batch(const ProjParams* Js, float gwInv, float ghInv) { const ProjParams J = Js[blockIdx.y]; proj_candidates_body<false>(J, gwInv, ghInv); }
 
 
 // The order-dependent loop, 256 queries per step on all four waves.  A query's decision (its first recorded candidates nobody has claimed) is final once
@@ -453,10 +464,11 @@ bool orbhip_proj_select_big(int n)
     return force || orbhip_proj_select_lds(n) > PJ_LDS_BUDGET;
 }
 
-void orbhip_launch_proj(const ProjParams& J, hipStream_t s)
+void orbhip_launch_proj(const ProjParams& J, hipStream_t s, bool fp_contract)
 {
     const float gwInv = (float)ORBHIP_GRID_COLS / (float)(J.max_x - J.min_x), ghInv = (float)ORBHIP_GRID_ROWS / (float)(J.max_y - J.min_y);
-    if (J.nq > 0) hipLaunchKernelGGL(k_proj_candidates, dim3((J.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, J, gwInv, ghInv);
+    if (J.nq > 0 && fp_contract) hipLaunchKernelGGL(k_proj_candidates_fc, dim3((J.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, J, gwInv, ghInv);
+    else if (J.nq > 0) hipLaunchKernelGGL(k_proj_candidates, dim3((J.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, J, gwInv, ghInv);
     if (J.big_ws) hipLaunchKernelGGL(k_proj_select_big, dim3(1, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(0), s, J);
     else hipLaunchKernelGGL(k_proj_select, dim3(1, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(J.n), s, J);
 }
@@ -477,14 +489,17 @@ void orbhip_launch_proj_batch(const ProjParams* d_slots, int nslots, int max_nq,
 // literals), FIRST smallest descriptor distance.  Queries do not interact: one wavefront per query scans the ordered bucket table
 // (cell ix*ROWS+iy, then index == GetFeaturesInArea's order; a key point within the radius always lies in a visited cell, see
 // k_match_candidates), lane-parallel, first-minimum by (distance, table position).
-__device__ __forceinline__ void best_in_window_body(const BestParams& B, int iq, int lane)
+// FC: the projection as in pj_project<true>, and the chi-square errors as gcc contracts them (read off the native build, ORBmatcher.cc:905-925):
+//   ex*ex+ey*ey          fma(ex, ex, ey*ey)
+//   ex*ex+ey*ey+er*er    fma(er, er, fma(ex, ex, ey*ey))
+template <bool FC> __device__ __forceinline__ void best_in_window_body(const BestParams& B, int iq, int lane)
 {
     if (iq >= B.nq) return;
     if (B.skip && ((B.skip[iq] >> B.skip_bit) & 1ull)) { if (lane == 0) { B.best_idx[iq] = -1; B.best_dist[iq] = 256; } return; }     // the point is in this key frame already (ORBmatcher.cc:848-849)
     orbhip_best_query q;
     if (B.pts) {
         PjOut o;
-        const bool live = pj_project(*B.proj, B.pts[iq], o);
+        const bool live = pj_project<FC>(*B.proj, B.pts[iq], o);
         q.x = live ? o.u : 0.0f; q.y = live ? o.v : 0.0f; q.radius = live ? o.radius : -1.0f; q.ur = live ? o.ur : 0.0f; q.level = live ? o.level : 0;
         if (lane == 0 && B.q_out) B.q_out[iq] = q;
         if (!live) { if (lane == 0) { B.best_idx[iq] = -1; B.best_dist[iq] = 256; } return; }
@@ -516,10 +531,10 @@ __device__ __forceinline__ void best_in_window_body(const BestParams& B, int iq,
                     const float ur = B.u_right ? B.u_right[idx] : -1.0f;
                     if (ur >= 0) {                                                                       // :901-914
                         const float er = __fsub_rn(q.ur, ur);
-                        const float e2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(er, er));
+                        const float e2 = FC ? __fmaf_rn(er, er, __fmaf_rn(ex, ex, __fmul_rn(ey, ey))) : __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(er, er));
                         ok = !((double)__fmul_rn(e2, B.inv_level_sigma2[lvl]) > 7.8);
                     } else {                                                                             // :915-926
-                        const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+                        const float e2 = FC ? __fmaf_rn(ex, ex, __fmul_rn(ey, ey)) : __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
                         ok = !((double)__fmul_rn(e2, B.inv_level_sigma2[lvl]) > 5.99);
                     }
                 }
@@ -544,20 +559,32 @@ __device__ __forceinline__ void best_in_window_body(const BestParams& B, int iq,
 }
 __global__ __launch_bounds__(256) void k_best_in_window(BestParams B)
 {
-    best_in_window_body(B, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    best_in_window_body<false>(B, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
 }
 // several key frames in one launch (orbhip_search_best_in_window_batch): parameter blocks in device memory, pref[s] = first block of slot s
 __global__ __launch_bounds__(256) void k_best_in_window_batch(const BestParams* Bs, const int* pref, int nslots)
 {
     int sl = 0; while (sl + 1 < nslots && (int)blockIdx.x >= pref[sl + 1]) sl++;
-    best_in_window_body(Bs[sl], ((int)blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    best_in_window_body<false>(Bs[sl], ((int)blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+}
+// the same two with the fused forms (ORBHIP_FP_CONTRACT): kernels of their own, so that the canonical ones' code is what it was
+__global__ __launch_bounds__(256) void k_best_in_window_fc(BestParams B)
+{
+    best_in_window_body<true>(B, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+}
+__global__ __launch_bounds__(256) void k_best_in_window_batch_fc(const BestParams* Bs, const int* pref, int nslots)
+{
+    int sl = 0; while (sl + 1 < nslots && (int)blockIdx.x >= pref[sl + 1]) sl++;
+    best_in_window_body<true>(Bs[sl], ((int)blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
 }
 
-void orbhip_launch_best_in_window(const BestParams& B, hipStream_t s)
+void orbhip_launch_best_in_window(const BestParams& B, hipStream_t s, bool fp_contract)
 {
-    if (B.nq > 0) hipLaunchKernelGGL(k_best_in_window, dim3((B.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, B);
+    if (B.nq > 0 && fp_contract) hipLaunchKernelGGL(k_best_in_window_fc, dim3((B.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, B);
+    else if (B.nq > 0) hipLaunchKernelGGL(k_best_in_window, dim3((B.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, B);
 }
-void orbhip_launch_best_in_window_batch(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s)
+void orbhip_launch_best_in_window_batch(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s, bool fp_contract)
 {
-    if (nblocks > 0) hipLaunchKernelGGL(k_best_in_window_batch, dim3(nblocks, 1, 1), dim3(256, 1, 1), 0, s, d_slots, d_pref, nslots);
+    if (nblocks > 0 && fp_contract) hipLaunchKernelGGL(k_best_in_window_batch_fc, dim3(nblocks, 1, 1), dim3(256, 1, 1), 0, s, d_slots, d_pref, nslots);
+    else if (nblocks > 0) hipLaunchKernelGGL(k_best_in_window_batch, dim3(nblocks, 1, 1), dim3(256, 1, 1), 0, s, d_slots, d_pref, nslots);
 }

@@ -78,6 +78,7 @@ class Bounds(C.Structure):          # orbhip_bounds: Frame::mnMinX, mnMinY, mnMa
 MAX_PROJ_LEVELS = 16
 LEVEL_OF = C.CFUNCTYPE(C.c_int, C.c_float, C.c_void_p)       # int level_of(float ratio, void* user): the caller's own PredictScale expression
 PROJ_LAST_FRAME, PROJ_FRAME_KF, PROJ_KF_SIM3, PROJ_FUSE, PROJ_FUSE_SIM3, PROJ_SIM3 = range(6)        # orbhip_projection_kind
+FP_CONTRACT = 0x100     # ORBHIP_FP_CONTRACT: OR-ed into Projection.kind / the triangulation entries' check_ori - gcc's fused forms of the members' statements (H3)
 
 
 class Projection(C.Structure):      # orbhip_projection: what one call of a pose-guided ORBmatcher member holds fixed
@@ -1008,8 +1009,9 @@ def search_by_bow(mode, desc1, angle1, valid1, fv1, desc2, angle2, valid2, fv2, 
 
 
 def search_for_triangulation(desc1, kps1, has_mp1, stereo1, fv1, desc2, kps2, has_mp2, stereo2, fv2, F12, ex, ey, scale_factors2, level_sigma2_2,
-                             only_stereo=False, check_ori=True, device=0, library=None):
-    """ORBmatcher::SearchForTriangulation (ORBmatcher.cc:657-823) on flat data; kps = KEYPOINT arrays (mvKeysUn).  -> (nmatches, match12[n1])"""
+                             only_stereo=False, check_ori=True, device=0, library=None, fp_contract=0):
+    """ORBmatcher::SearchForTriangulation (ORBmatcher.cc:657-823) on flat data; kps = KEYPOINT arrays (mvKeysUn).  -> (nmatches, match12[n1])
+    fp_contract=1: the epipolar-line / epipole statements in gcc's fused forms (FP_CONTRACT)"""
     L = lib(library)
     kp4 = lambda k: np.ascontiguousarray(np.stack([k["x"], k["y"], k["angle"], k["octave"].astype(np.float32)], axis=1), np.float32)
     desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
@@ -1023,7 +1025,7 @@ def search_for_triangulation(desc1, kps1, has_mp1, stereo1, fv1, desc2, kps2, ha
     nm = C.c_int(0)
     _check(L.orbhip_search_for_triangulation(device, _p(desc1), _p(k1), _p(a[0]), _p(a[1]), len(desc1), _p(f1[0]), _p(f1[1]), _p(f1[2]), len(f1[0]),
                                              _p(desc2), _p(k2), _p(a[2]), _p(a[3]), len(desc2), _p(f2[0]), _p(f2[1]), _p(f2[2]), len(f2[0]),
-                                             _p(F), float(ex), float(ey), _p(sc), _p(sg), len(sc), int(only_stereo), int(check_ori), _p(m12), C.byref(nm)),
+                                             _p(F), float(ex), float(ey), _p(sc), _p(sg), len(sc), int(only_stereo), int(check_ori) | _fc(fp_contract), _p(m12), C.byref(nm)),
            "orbhip_search_for_triangulation", L)
     return nm.value, m12
 
@@ -1078,7 +1080,7 @@ def search_by_bow_batch(mode, pairs, nnratio=0.7, check_ori=True, device=0, libr
     return [(int(arr[k].nmatches), outs[k]) for k in range(len(pairs))]
 
 
-def search_for_triangulation_batch(kf1, neighbours, only_stereo=False, check_ori=False, device=0, library=None):
+def search_for_triangulation_batch(kf1, neighbours, only_stereo=False, check_ori=False, device=0, library=None, fp_contract=0):
     """orbhip_search_for_triangulation_batch.  kf1 / a neighbour's "kf" = dict(desc=, kps= (KEYPOINT array, mvKeysUn), has_mp=, stereo=, fv=, scale_factors=, level_sigma2=);
     neighbours = [dict(kf=..., F12=, ex=, ey=), ...].  Every pair is searched with kf1's has_mp as given.  -> [(nmatches, match12[n1]), ...]"""
     L = lib(library)
@@ -1100,7 +1102,7 @@ def search_for_triangulation_batch(kf1, neighbours, only_stereo=False, check_ori
         for i, v in enumerate(np.ascontiguousarray(nb["F12"], np.float32).reshape(9)):
             arr[k].F12[i] = float(v)
         arr[k].ex = float(nb["ex"]); arr[k].ey = float(nb["ey"]); arr[k].match12 = _p(m12).value if len(m12) else None
-    _check(L.orbhip_search_for_triangulation_batch(device, C.byref(s1), len(neighbours), arr, int(only_stereo), int(check_ori)), "orbhip_search_for_triangulation_batch", L)
+    _check(L.orbhip_search_for_triangulation_batch(device, C.byref(s1), len(neighbours), arr, int(only_stereo), int(check_ori) | _fc(fp_contract)), "orbhip_search_for_triangulation_batch", L)
     return [(int(arr[k].nmatches), outs[k]) for k in range(len(neighbours))]
 
 
@@ -1164,9 +1166,23 @@ def predict_scale_table(log_scale_factor, nlevels, level_of=None, library=None):
     return out
 
 
-def make_projection(kind, R, t, fx, fy, cx, cy, bounds, th, scale_factors, level_ratio, Ow=(0, 0, 0), bf=0.0, R2=None, t2=None, gemm_mode=0, forward=False, backward=False):
+def _fc(fp_contract):
+    return FP_CONTRACT if fp_contract else 0
+
+
+def _proj_fc(proj, fp_contract):
+    """proj itself (fp_contract=0), or a copy with FP_CONTRACT in its kind"""
+    if not fp_contract:
+        return proj
+    P = Projection.from_buffer_copy(proj)
+    P.kind |= FP_CONTRACT
+    return P
+
+
+def make_projection(kind, R, t, fx, fy, cx, cy, bounds, th, scale_factors, level_ratio, Ow=(0, 0, 0), bf=0.0, R2=None, t2=None, gemm_mode=0, forward=False, backward=False,
+                    fp_contract=0):
     P = Projection()
-    P.kind = kind; P.gemm_mode = gemm_mode
+    P.kind = kind | _fc(fp_contract); P.gemm_mode = gemm_mode
     P.R = (C.c_float * 9)(*np.asarray(R, np.float32).reshape(9)); P.t = (C.c_float * 3)(*np.asarray(t, np.float32).reshape(3))
     if R2 is not None:
         P.R2 = (C.c_float * 9)(*np.asarray(R2, np.float32).reshape(9)); P.t2 = (C.c_float * 3)(*np.asarray(t2, np.float32).reshape(3))
@@ -1181,9 +1197,11 @@ def make_projection(kind, R, t, fx, fy, cx, cy, bounds, th, scale_factors, level
     return P
 
 
-def project_search(kps, desc, bounds, proj, points, point_desc, nnratio=0.9, th_high=100, check_ori=True, u_right=None, blocked=None, device=0, library=None):
-    """orbhip_project_search_bounds -> (nmatches, feature_query[n], queries_out[np]): the projection of the pose-guided SearchByProjection overloads on the device"""
+def project_search(kps, desc, bounds, proj, points, point_desc, nnratio=0.9, th_high=100, check_ori=True, u_right=None, blocked=None, device=0, library=None, fp_contract=0):
+    """orbhip_project_search_bounds -> (nmatches, feature_query[n], queries_out[np]): the projection of the pose-guided SearchByProjection overloads on the device.
+    fp_contract=1: FP_CONTRACT added to proj's kind (gcc's fused forms)"""
     L = lib(library)
+    proj = _proj_fc(proj, fp_contract)
     kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
     points = np.ascontiguousarray(points, MAP_POINT_DTYPE); point_desc = np.ascontiguousarray(point_desc, np.uint8)
     ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
@@ -1195,9 +1213,11 @@ def project_search(kps, desc, bounds, proj, points, point_desc, nnratio=0.9, th_
     return nm.value, fq, qo
 
 
-def project_best_in_window(kps, desc, bounds, inv_level_sigma2, proj, points, point_desc, chi2_gate, u_right=None, device=0, library=None):
-    """orbhip_project_best_in_window_bounds -> (best_idx[np], best_dist[np], queries_out[np]): Fuse x2 / SearchBySim3 with the projection on the device"""
+def project_best_in_window(kps, desc, bounds, inv_level_sigma2, proj, points, point_desc, chi2_gate, u_right=None, device=0, library=None, fp_contract=0):
+    """orbhip_project_best_in_window_bounds -> (best_idx[np], best_dist[np], queries_out[np]): Fuse x2 / SearchBySim3 with the projection on the device
+    (fp_contract as in project_search)"""
     L = lib(library)
+    proj = _proj_fc(proj, fp_contract)
     kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
     points = np.ascontiguousarray(points, MAP_POINT_DTYPE); point_desc = np.ascontiguousarray(point_desc, np.uint8)
     inv = np.ascontiguousarray(inv_level_sigma2, np.float32)
@@ -1214,8 +1234,9 @@ class ProjectBestSlot(C.Structure):  # orbhip_project_best_slot
                 ("proj", C.POINTER(Projection)), ("points", C.c_void_p), ("point_desc", C.c_void_p), ("np", C.c_int32), ("best_idx", C.c_void_p), ("best_dist", C.c_void_p)]
 
 
-def project_best_in_window_batch(slots, chi2_gate, device=0, library=None):
-    """orbhip_project_best_in_window_batch.  slots = [dict(kps=, desc=, u_right= (or None), bounds=, inv_level_sigma2=, proj=, points=, pdesc=), ...] -> [(best_idx, best_dist), ...]"""
+def project_best_in_window_batch(slots, chi2_gate, device=0, library=None, fp_contract=0):
+    """orbhip_project_best_in_window_batch.  slots = [dict(kps=, desc=, u_right= (or None), bounds=, inv_level_sigma2=, proj=, points=, pdesc=), ...] -> [(best_idx, best_dist), ...]
+    (fp_contract=1: FP_CONTRACT added to every slot's kind)"""
     L = lib(library)
     keep, outs = [], []
     arr = (ProjectBestSlot * max(len(slots), 1))()
@@ -1225,17 +1246,18 @@ def project_best_in_window_batch(slots, chi2_gate, device=0, library=None):
         inv = np.ascontiguousarray(sl["inv_level_sigma2"], np.float32)
         ur = None if sl.get("u_right") is None else np.ascontiguousarray(sl["u_right"], np.float32)
         bi = np.full(len(pts), -1, np.int32); bd = np.full(len(pts), 256, np.int32)
-        keep.extend([kps, desc, pts, pd, inv, ur, sl["proj"]]); outs.append((bi, bd))
+        proj = _proj_fc(sl["proj"], fp_contract)
+        keep.extend([kps, desc, pts, pd, inv, ur, proj]); outs.append((bi, bd))
         a = arr[k]
         a.kps = _p(kps).value if len(kps) else None; a.desc = _p(desc).value if len(desc) else None; a.u_right = None if ur is None else _p(ur).value; a.n = len(kps)
         a.bounds = Bounds.of(sl["bounds"]); a.inv_level_sigma2 = _p(inv).value; a.nlevels = len(inv)
-        a.proj = C.pointer(sl["proj"]); a.points = _p(pts).value if len(pts) else None; a.point_desc = _p(pd).value if len(pd) else None; a.np = len(pts)
+        a.proj = C.pointer(proj); a.points = _p(pts).value if len(pts) else None; a.point_desc = _p(pd).value if len(pd) else None; a.np = len(pts)
         a.best_idx = _p(bi).value if len(pts) else None; a.best_dist = _p(bd).value if len(pts) else None
     _check(L.orbhip_project_best_in_window_batch(device, len(slots), arr, int(chi2_gate)), "orbhip_project_best_in_window_batch", L)
     return outs
 
 
-def project_best_in_window_shared(slots, points, pdesc, skip, chi2_gate, device=0, library=None):
+def project_best_in_window_shared(slots, points, pdesc, skip, chi2_gate, device=0, library=None, fp_contract=0):
     """orbhip_project_best_in_window_shared: ONE set of points (uploaded once) offered to every slot; skip[k] bit s set = point k is not searched in slot s.
     slots = [dict(kps=, desc=, u_right= (or None), bounds=, inv_level_sigma2=, proj=), ...] -> [(best_idx, best_dist), ...]"""
     L = lib(library)
@@ -1248,20 +1270,22 @@ def project_best_in_window_shared(slots, points, pdesc, skip, chi2_gate, device=
         inv = np.ascontiguousarray(sl["inv_level_sigma2"], np.float32)
         ur = None if sl.get("u_right") is None else np.ascontiguousarray(sl["u_right"], np.float32)
         bi = np.full(len(pts), -1, np.int32); bd = np.full(len(pts), 256, np.int32)
-        keep.extend([kps, desc, inv, ur, sl["proj"]]); outs.append((bi, bd))
+        proj = _proj_fc(sl["proj"], fp_contract)
+        keep.extend([kps, desc, inv, ur, proj]); outs.append((bi, bd))
         a = arr[k]
         a.kps = _p(kps).value if len(kps) else None; a.desc = _p(desc).value if len(desc) else None; a.u_right = None if ur is None else _p(ur).value; a.n = len(kps)
         a.bounds = Bounds.of(sl["bounds"]); a.inv_level_sigma2 = _p(inv).value; a.nlevels = len(inv)
-        a.proj = C.pointer(sl["proj"]); a.points = _p(pts).value if len(pts) else None; a.point_desc = _p(pd).value if len(pd) else None; a.np = len(pts)
+        a.proj = C.pointer(proj); a.points = _p(pts).value if len(pts) else None; a.point_desc = _p(pd).value if len(pd) else None; a.np = len(pts)
         a.best_idx = _p(bi).value if len(pts) else None; a.best_dist = _p(bd).value if len(pts) else None
     _check(L.orbhip_project_best_in_window_shared(device, len(slots), arr, None if sk is None else _p(sk), int(chi2_gate)), "orbhip_project_best_in_window_shared", L)
     return outs
 
 
-def project_best_in_window_held(slot, proj, points, pdesc, chi2_gate, device=0, library=None, check=True):
+def project_best_in_window_held(slot, proj, points, pdesc, chi2_gate, device=0, library=None, check=True, fp_contract=0):
     """orbhip_project_best_in_window_held: slot `slot` of this thread's last project_best_in_window_shared call searched again with other points.
     check=False: returns (status, best_idx, best_dist) instead of raising"""
     L = lib(library)
+    proj = _proj_fc(proj, fp_contract)
     pts = np.ascontiguousarray(points, MAP_POINT_DTYPE); pd = np.ascontiguousarray(pdesc, np.uint8)
     bi = np.full(len(pts), -1, np.int32); bd = np.full(len(pts), 256, np.int32)
     st = L.orbhip_project_best_in_window_held(device, int(slot), C.byref(proj), _p(pts), _p(pd), len(pts), int(chi2_gate), _p(bi), _p(bd))
