@@ -19,16 +19,21 @@ The timed region is EXACTLY `--steps` steps, bracketed by barrier + synchronize;
 `--dump-outputs DIR` writes what the last timed step handed its caller (key points, descriptors, matches12 of a fixed sample of camera
 slots) as DIR/<name>.npy, float32 / float64, so that two builds run with the same arguments (the inputs are seeded) can be compared.
 
-Extra objects in the JSON line:
+A plain run does only what the headline figure needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line,
+with the per-kernel times and the roofline the timed region's own HIP events give.  `--full` adds everything else below (each `--no-*`
+option then drops one part of it).
+
+Extra objects in the JSON line, with --full:
   parity        key points, descriptors and matches12 of one camera slot per DISTINCT scene (64) of the LAST timed step compared bit for bit with the
                 oracle, and every replica slot of a scene with the first slot of that scene: the whole batch; a mismatch marks the line INVALID
   runtime       the HIP runtime the library ran on (versions, file), every libamdhip64 mapped into the process (must be one)
-  roofline      dominant kernel (by HIP-event time measured inside the timed region on the library's stream):
+  roofline      dominant kernel (by HIP-event time measured inside the timed region on the library's stream, in a plain run too):
                 algorithmic bytes per launch / average launch duration vs the 8 TB/s HBM peak; `traffic` = HBM bytes per launch from
                 two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; gfx950 correction) over a short child run of the same workload;
                 `bound` = what the evidence says limits the kernel
   roofline_valu the same kernel against its VALU-issue floor: instructions per wave x waves x 4 cycles / (1024 SIMDs x 2.4 GHz), and against the
                 clock it actually ran at (GRBM_GUI_ACTIVE / dispatch time in a fourth --pmc child pass): clock_GHz_effective, frac_at_effective_clock
+                (a plain run quotes the instruction counts of the newest committed PMC summary and runs no child pass)
   dropin_loop   the drop-in as ORB_SLAM2 drives it: >= 20 stereo frames through the reference's own Frame.cc / ORBmatcher.cc (stereo Frame
                 constructor, ComputeStereoMatches, SearchByProjection(Current, Last), SearchByProjection(Frame, MapPoints)), ms per frame with
                 the drop-in on the GPU and with the reference on the host, bit-exact per frame (KITTI shape; EuRoC shape under "euroc")
@@ -286,8 +291,7 @@ def hbm_traffic_subprocess(dom, B, args):
     for counter in ("FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU SQ_WAVES", "GRBM_GUI_ACTIVE"):
         d = tempfile.mkdtemp(prefix="orb_pmc_", dir="/tmp")
         cmd = ["rocprofv3", "--pmc"] + counter.split() + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
-               "--batch", str(B), "--steps", "3", "--warmup", "1", "--repeats", "1", "--streams", str(args.streams), "--blur-round-mode", str(args.blur_round_mode),
-               "--no-cpu-baseline", "--no-host-io", "--no-dropin-loop", "--no-traffic", "--no-secondary", "--parity-slots", "0"]
+               "--batch", str(B), "--steps", "3", "--warmup", "1", "--repeats", "1", "--streams", str(args.streams), "--blur-round-mode", str(args.blur_round_mode)]   # a plain run
         try:
             r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True, timeout=300)
             files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
@@ -477,7 +481,7 @@ def pool_mode(args):
 
 
 def multi_gpu_extras(args, G, share):
-    """What `--gpus N` adds for N > 1 after the resident measurement, on rank 0 while the other ranks wait (their contexts closed): the two multi-GPU curves that
+    """What `--gpus N --full` adds for N > 1 after the resident measurement, on rank 0 while the other ranks wait (their contexts closed): the two multi-GPU curves that
     CAN bend - the device-resident rate moves nothing over PCIe and is linear by construction.
       host_io_pool     ONE process feeding all G devices from host buffers through the pool (orbhip_pool_*: a worker thread + context + pinned ring per device, camera
                        c on device c mod G), pinned and pageable caller buffers, rounds pipelined two deep: frames/s, per-device share, the NUMA placement of every worker
@@ -553,6 +557,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=1, help="measurements of --steps steps each; value = the median one")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (a fixed sample of camera slots, at most 64 MB) "
                     "as DIR/<name>.npy in float32 / float64; rank 0")
+    ap.add_argument("--full", action="store_true", help="after the headline figure also run the oracle parity check, the rocprofv3 traffic / clock passes, host_io, "
+                    "dropin_loop, the secondary units, the CPU baseline and (N > 1) the multi-GPU extras; the --no-* options drop parts of it")
     ap.add_argument("--no-host-io", action="store_true", help="skip the PCIe-inclusive host-buffer measurement (host_io object)")
     ap.add_argument("--batch", type=int, default=512, help="camera slots (frames) per step per GPU")
     ap.add_argument("--tsteps", type=int, default=4, help="distinct resident time steps cycled through")
@@ -568,9 +574,9 @@ def main():
     ap.add_argument("--pool", action="store_true", help="time the one-process multi-GPU pool (orbhip_pool_*: one host thread per GPU) at the host-buffer boundary instead of "
                     "the one-process-per-GPU device-resident benchmark; prints its own JSON line (mode: pool)")
     ap.add_argument("--pool-cameras-per-gpu", type=int, default=128)
-    ap.add_argument("--parity-slots", type=int, default=NSCENES, help="camera slots of the last timed step compared bit for bit with the oracle: by default one per distinct scene, "
+    ap.add_argument("--parity-slots", type=int, default=NSCENES, help="with --full or --pool: camera slots of the last timed step compared bit for bit with the oracle: by default one per distinct scene, "
                     "i.e. with the replica check every frame of the step (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="N > 1: skip the host-fed pool and the sharded descriptor database that rank 0 measures after the resident run")
+    ap.add_argument("--no-extras", action="store_true", help="N > 1, with --full: skip the host-fed pool and the sharded descriptor database that rank 0 measures after the resident run")
     ap.add_argument("--extras-cameras-per-gpu", type=int, default=64)
     ap.add_argument("--extras-rounds", type=int, default=12)
     ap.add_argument("--extras-db-keyframes", type=int, default=10000, help="key frames (x 2000 descriptors) of the sharded database of config5_sharded")
@@ -591,6 +597,9 @@ def main():
         return
     if args.pool:
         return pool_mode(args)
+    if not args.full:                                                 # a plain run: the headline figure (and --dump-outputs) only
+        args.parity_slots = 0
+        args.no_traffic = args.no_host_io = args.no_dropin_loop = args.no_secondary = args.no_cpu_baseline = args.no_extras = True
 
     # No framework in this process, at any N: the library runs on the HIP runtime its RUNPATH names (/opt/rocm — the one the tests, smoke()
     # and a real ORB_SLAM2 binary use), frames are made resident through the library (orbhip_device_alloc), and the ranks of an N > 1 run

@@ -137,7 +137,7 @@ def test_bench_gpus_flag_on_this_box():
 
 @pytest.mark.gpu
 def test_bench_three_ranks_on_one_gpu():
-    """The multi-GPU command, first time right: `bench.py --gpus 3` becomes its own launcher, three ranks rendezvous, every rank builds its
+    """The multi-GPU command, first time right: `bench.py --gpus 3 --full` becomes its own launcher, three ranks rendezvous, every rank builds its
     resident batch and context, the timed region is bracketed by the 3-way barrier, rank 0 prints ONE JSON line with n_gpus = 3 and a
     bit-exact parity object; three shards also split the descriptor database unevenly.  The ranks share this box's GPU
     (ORB_BENCH_SHARE_GPU=1: a test aid bench.py names in its config line; the number it prints is not a scaling figure).  Three ranks, not
@@ -148,7 +148,7 @@ def test_bench_three_ranks_on_one_gpu():
     env = dict(os.environ); env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     env["ORB_BENCH_SHARE_GPU"] = "1"
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--batch", "32", "--steps", "3", "--warmup", "1", "--repeats", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--batch", "32", "--steps", "3", "--warmup", "1", "--repeats", "2", "--full",
                         "--no-cpu-baseline", "--no-host-io", "--no-traffic", "--no-dropin-loop",
                         "--extras-cameras-per-gpu", "4", "--extras-rounds", "3", "--extras-db-keyframes", "40"], env=env, capture_output=True, text=True, timeout=1200)
     wall = time.time() - t0
@@ -167,6 +167,34 @@ def test_bench_three_ranks_on_one_gpu():
     assert max(c5["rows_per_shard"]) - min(c5["rows_per_shard"]) == 1
     assert d["per_rank"]["frames_per_s_fastest_rank"] >= d["per_rank"]["frames_per_s_slowest_rank"] > 0
     print(f"\n[3 ranks on one GPU] launcher + 3 ranks + rendezvous + run: {wall:.1f} s wall; {d['value']:.0f} frames/s over the shared GPU (not a scaling figure)")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only():
+    """`bench.py --gpus 1` without --full: the headline line and --dump-outputs, none of what --full adds (the oracle parity check, the
+    rocprofv3 passes, host_io, dropin_loop, the secondary units, the CPU baseline); --full at the same shape adds the parity check."""
+    import json
+    import subprocess
+    import tempfile
+    env = dict(os.environ); env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None); env.pop("ORB_BENCH_SHARE_GPU", None)
+    small = ["--gpus", "1", "--batch", "32", "--steps", "3", "--warmup", "1"]
+    with tempfile.TemporaryDirectory() as dump:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + small + ["--dump-outputs", dump], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["metric"].startswith("frames/s ORB extract+match") and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["parity"] is None and "INVALID" not in d and d["roofline"]["traffic"] is None and "traffic_measured" not in d["roofline"]
+        for key in ("host_io", "dropin_loop", "matcher_calls", "config5", "config4", "cpu_baseline", "host_io_pool", "config5_sharded"):
+            assert key not in d, key
+        assert d["dump_outputs"]["slots"] == 32 and sorted(os.listdir(dump)) == sorted(f + ".npy" for f in d["dump_outputs"]["files"])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + small + ["--full", "--parity-slots", "4", "--no-traffic", "--no-host-io", "--no-dropin-loop",
+                        "--no-secondary", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["parity"]["slots"] == 4 and d["parity"]["mismatches"] == 0 and d["parity"]["replica_slots_checked"] == 0 and "INVALID" not in d
 
 
 def _rdzv_worker(rank, world, key, q):

@@ -5,8 +5,8 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 for round in 1 2 3; do
-  ORBHIP_LIBRARY=$(pwd)/ab/liborbhip_$NAME.so timeout 300 python3 bench.py --steps 50 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-io "$@" >> $OUT/bench_A_$NAME.jsonl 2>> $OUT/bench.err
-  timeout 300 python3 bench.py --steps 50 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-io "$@" >> $OUT/bench_B_new.jsonl 2>> $OUT/bench.err
+  ORBHIP_LIBRARY=$(pwd)/ab/liborbhip_$NAME.so timeout 300 python3 bench.py --full --steps 50 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-io "$@" >> $OUT/bench_A_$NAME.jsonl 2>> $OUT/bench.err
+  timeout 300 python3 bench.py --full --steps 50 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-io "$@" >> $OUT/bench_B_new.jsonl 2>> $OUT/bench.err
 done
 python3 - <<PY
 import json

@@ -10,7 +10,7 @@ for round in $(seq $ROUNDS); do
     IFS='|' read -r label lib envs args <<< "$spec"
     ( [ "$lib" != "-" ] && export ORBHIP_LIBRARY=$(pwd)/ab/liborbhip_$lib.so
       for e in $envs; do export $e; done
-      timeout 300 python3 bench.py --steps 50 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-io $args >> $OUT/bench_$label.jsonl 2>> $OUT/bench.err )
+      timeout 300 python3 bench.py --full --steps 50 --warmup 3 --repeats 3 --no-cpu-baseline --no-host-io $args >> $OUT/bench_$label.jsonl 2>> $OUT/bench.err )
   done
 done
 python3 - "$OUT" "$@" <<'PY'

@@ -11,8 +11,8 @@ done
 sort $OUT/single.txt
 NROWS=7 tools/gpu_trace_variant.sh $TAG new | grep -v "^W2026" | tail -8
 for r in 1 2; do
-  timeout 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-host-io --no-traffic --no-dropin-loop > $OUT/bench_new_$r.json 2>> $OUT/bench.err
-  ORBHIP_LIBRARY=$R/ab/liborbhip_prev.so timeout 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-host-io --no-traffic --no-dropin-loop > $OUT/bench_prev_$r.json 2>> $OUT/bench.err
+  timeout 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-host-io --no-traffic --no-dropin-loop > $OUT/bench_new_$r.json 2>> $OUT/bench.err
+  ORBHIP_LIBRARY=$R/ab/liborbhip_prev.so timeout 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-host-io --no-traffic --no-dropin-loop > $OUT/bench_prev_$r.json 2>> $OUT/bench.err
 done
 python3 - <<PY
 import json

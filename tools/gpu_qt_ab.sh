@@ -9,7 +9,7 @@ for r in 1 2; do
 done
 for n in new prev; do
   [ $n = prev ] && export ORBHIP_LIBRARY=$R/ab/liborbhip_prev.so || unset ORBHIP_LIBRARY
-  timeout 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-host-io --no-traffic --no-dropin-loop 2>/dev/null | python3 -c "
+  timeout 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-host-io --no-traffic --no-dropin-loop 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$n', j['value'], j['parity']['mismatches'], {k: round(v,4) for k,v in j['kernels_ms_per_launch'].items() if v})"
   ORBHIP_SERIAL=1 timeout 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-io --no-traffic --no-dropin-loop 2>/dev/null | python3 -c "
