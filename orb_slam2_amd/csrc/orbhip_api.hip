@@ -1524,21 +1524,7 @@ static orbhip_status frame_args(orbhip_ctx* c, int frame, int n, int use_u_right
     return ORBHIP_OK;
 }
 
-#ifdef ORBHIP_TEST_HOOKS
-// The CPU emulation build only: ORBHIP_TEST_RECORD=<file> appends every projected search (its inputs as the C ABI received them and its answers) to <file> -
-// how tests/golden/make_golden_native_matcher.py captures what the drop-in classes hand the device, for a replay through liborbhip.so.  A record: int32 tag
-// (1 = orbhip_project_search_*, 2 = one slot of orbhip_project_best_in_window_*), then length-prefixed (int64 bytes) arrays in a fixed order.
-static std::mutex g_record_mutex;
-struct TestRecord {
-    FILE* f = nullptr; std::unique_lock<std::mutex> lock;
-    explicit TestRecord(int tag) : lock(g_record_mutex) { const char* p = getenv("ORBHIP_TEST_RECORD"); if (p && *p && (f = fopen(p, "ab"))) fwrite(&tag, 4, 1, f); }
-    ~TestRecord() { if (f) fclose(f); }
-    template <typename T> void put(const T* a, size_t count) { if (!f) return; const long long b = a ? (long long)(count * sizeof(T)) : -1; fwrite(&b, 8, 1, f); if (a && count) fwrite(a, sizeof(T), count, f); }
-};
-#define ORBHIP_RECORD(...) do { __VA_ARGS__ } while (0)
-#else
-#define ORBHIP_RECORD(...) do { } while (0)
-#endif
+// (ORBHIP_RECORD / TestRecord, the emulation-only capture of the calls below: orbhip_internal.h)
 
 // queries given (P == nullptr) or derived on the device from map points under *P (orbhip_project_search_*): `queries` is then nullptr and nq = the point count
 static orbhip_status search_by_projection(const SearchFrame& F, const uint8_t* blocked, const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,

@@ -1131,6 +1131,12 @@ extern "C" orbhip_status orbhip_search_for_triangulation(int device,
     if (e == hipSuccess) e = arena_download(ts);
     if (e != hipSuccess) { (void)hipStreamSynchronize(ts); for (int i = 0; i < n1; i++) match12[i] = -1; return orbhip_set_error(ORBHIP_ERR_HIP, "search_for_triangulation: %s", hipGetErrorString(e)); }
     *nmatches = tail[ORBHIP_HISTO_LENGTH];
+    ORBHIP_RECORD(
+        TestRecord R(3); const float epi[2] = {ex, ey}; const int ipar[3] = {only_stereo, check_ori, *nmatches};
+        R.put(desc1, (size_t)n1 * 32); R.put(kp1, (size_t)n1 * 4); R.put(has_mp1, n1); R.put(stereo1, n1); R.put(fv1_node, nfv1); R.put(fv1_off, (size_t)nfv1 + 1); R.put(fv1_feat, m1);
+        R.put(desc2, (size_t)n2 * 32); R.put(kp2, (size_t)n2 * 4); R.put(has_mp2, n2); R.put(stereo2, n2); R.put(fv2_node, nfv2); R.put(fv2_off, (size_t)nfv2 + 1); R.put(fv2_feat, m2);
+        R.put(F12, 9); R.put(epi, 2); R.put(scale_factors2, nlevels2); R.put(level_sigma2_2, nlevels2); R.put(ipar, 3); R.put(match12, n1);
+    );
     return ORBHIP_OK;
 }
 
@@ -1289,5 +1295,12 @@ extern "C" orbhip_status orbhip_search_for_triangulation_batch(int device, const
         return orbhip_set_error(ORBHIP_ERR_HIP, "search_for_triangulation_batch: %s", hipGetErrorString(e));
     }
     for (int k = 0; k < NL; k++) pairs[live[k]].nmatches = tail[k][ORBHIP_HISTO_LENGTH];
+    ORBHIP_RECORD(for (int k = 0; k < NL; k++) {               // one record per pair, the arrays of orbhip_search_for_triangulation in the same order
+        const orbhip_tri_pair& Q = pairs[live[k]]; const orbhip_tri_side &a = *kf1, &b = *Q.kf2;
+        TestRecord R(3); const float epi[2] = {Q.ex, Q.ey}; const int ipar[3] = {only_stereo, check_ori, Q.nmatches};
+        R.put(a.desc, (size_t)a.n * 32); R.put(a.kp, (size_t)a.n * 4); R.put(a.has_mp, a.n); R.put(a.stereo, a.n); R.put(a.fv_node, a.nfv); R.put(a.fv_off, (size_t)a.nfv + 1); R.put(a.fv_feat, a.fv_off[a.nfv]);
+        R.put(b.desc, (size_t)b.n * 32); R.put(b.kp, (size_t)b.n * 4); R.put(b.has_mp, b.n); R.put(b.stereo, b.n); R.put(b.fv_node, b.nfv); R.put(b.fv_off, (size_t)b.nfv + 1); R.put(b.fv_feat, b.fv_off[b.nfv]);
+        R.put(Q.F12, 9); R.put(epi, 2); R.put(b.scale_factors, b.nlevels); R.put(b.level_sigma2, b.nlevels); R.put(ipar, 3); R.put(Q.match12, a.n);
+    });
     return ORBHIP_OK;
 }

@@ -270,3 +270,21 @@ struct OrbApiTimer {
 void orbhip_touch_thread_caches();      // makes sure the calling thread's cache holder exists (its destructor releases the caches of worker threads)
 orbhip_status orbhip_set_error(orbhip_status st, const char* fmt, ...);
 void orbhip_internal_outputs(orbhip_ctx* c, const uint8_t** d_desc, const int** d_n, int* cap, int* last_nimg, int* device, hipStream_t* s);
+
+#ifdef ORBHIP_TEST_HOOKS
+#include <cstdio>
+#include <mutex>
+// The CPU emulation build only: ORBHIP_TEST_RECORD=<file> appends every projected search and every triangulation search (its inputs as the C ABI received them and its answers) to <file> -
+// how tests/golden/make_golden_native_matcher.py captures what the drop-in classes hand the device, for a replay through liborbhip.so.  A record: int32 tag
+// (1 = orbhip_project_search_*, 2 = one slot of orbhip_project_best_in_window_*, 3 = orbhip_search_for_triangulation or one pair of its batch form), then length-prefixed (int64 bytes) arrays in a fixed order.
+inline std::mutex g_record_mutex;
+struct TestRecord {
+    FILE* f = nullptr; std::unique_lock<std::mutex> lock;
+    explicit TestRecord(int tag) : lock(g_record_mutex) { const char* p = getenv("ORBHIP_TEST_RECORD"); if (p && *p && (f = fopen(p, "ab"))) fwrite(&tag, 4, 1, f); }
+    ~TestRecord() { if (f) fclose(f); }
+    template <typename T> void put(const T* a, size_t count) { if (!f) return; const long long b = a ? (long long)(count * sizeof(T)) : -1; fwrite(&b, 8, 1, f); if (a && count) fwrite(a, sizeof(T), count, f); }
+};
+#define ORBHIP_RECORD(...) do { __VA_ARGS__ } while (0)
+#else
+#define ORBHIP_RECORD(...) do { } while (0)
+#endif
