@@ -1,4 +1,4 @@
-// orbhip_internal.h — layouts shared by the host orchestration (orbhip_api.cpp) and the gfx950 kernels.
+// orbhip_internal.h — layouts shared by the host orchestration (orbhip_api.hip, orbhip_host_path.hip, orbhip_search.hip, orbhip_frame.hip; their own header: orbhip_ctx.h) and the gfx950 kernels.
 //
 // HBM layout of one context (fixed W x H, B = max_batch camera slots); all arrays are [frame][...]:
 //   planes      u8   per frame: levels 0..L-1, level l at plane_off[l], row pitch[l] (multiple of 64 B).

@@ -220,9 +220,8 @@ __global__ __launch_bounds__(256) void k_copy16(uint4* __restrict__ dst, const u
 }
 hipError_t orbhip_copy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s)
 {
-    static const bool dma_only = [] { const char* e = getenv("ORBHIP_COPY_KERNELS"); return e && *e == '0'; }();      // ORBHIP_COPY_KERNELS=0: every copy on the DMA engines
     if (bytes == 0) return hipSuccess;
-    if (dma_only || bytes > ((size_t)2 << 20) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return hipMemcpyAsync(dst, src, bytes, kind, s);
+    if (bytes > ((size_t)2 << 20) || (((uintptr_t)dst | (uintptr_t)src) & 15)) return hipMemcpyAsync(dst, src, bytes, kind, s);
     const long long n16 = (long long)(bytes >> 4);
     hipLaunchKernelGGL(k_copy16, dim3((unsigned)std::max<long long>((n16 + 255) / 256, 1), 1, 1), dim3(256, 1, 1), 0, s, (uint4*)dst, (const uint4*)src, n16, (int)(bytes & 15));
     return hipGetLastError();

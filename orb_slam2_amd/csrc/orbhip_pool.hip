@@ -4,7 +4,7 @@
 // The reference's only concurrency on this path is the pair of std::threads that run the left and right extractor of a stereo Frame
 // (Frame.cc:78-81).  A pool is that idea at node scale: devices[r] gets a worker thread that owns an extractor context (camera c is
 // served by devices[c mod G]) and, for the relocalisation query of config 5, the rows [lo_r, hi_r) of the descriptor DB.  Workers never
-// exchange data: a round of frames is G independent submit/collect pairs on the pipelined host path (orbhip_api.hip), a DB query is G
+// exchange data: a round of frames is G independent submit/collect pairs on the pipelined host path (orbhip_host_path.hip), a DB query is G
 // independent uploads of the same 64 KB query + G shard scans whose per-query (best, second, index) triples are merged on the host
 // with the matcher's rule — 2000 x G x 16 B, not worth an all-gather over xGMI.
 #include "orbhip_internal.h"
@@ -75,7 +75,7 @@ static orbhip_status pool_status(orbhip_pool* p, const char* what)
 // result scatters) and pinned ring live on the other socket pay a cross-socket hop on every byte, and at 8 GPUs x ~55 GB/s of uploads the host side
 // is what bends the scaling curve.  Each worker therefore binds itself to the CPUs of its device's NUMA node BEFORE it creates its context:
 // the context's pinned mirrors (hipHostMalloc, first touched by this thread) then come from that node's memory.  ORBHIP_POOL_NUMA=0 turns it off.
-// (orbhip_device_numa_node / orbhip_bind_thread_to_node live in orbhip_api.hip: the host path's copy helpers are placed with them too)
+// (orbhip_device_numa_node / orbhip_bind_thread_to_node live in orbhip_host_path.hip: the host path's copy helpers are placed with them too)
 
 extern "C" void orbhip_pool_destroy(orbhip_pool* p)
 {

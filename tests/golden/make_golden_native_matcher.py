@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 from oracle import orbslam_ref as S  # noqa: E402
 import test_native_flags_matcher_exact as E  # noqa: E402
 
-# the arrays of a record, in the order orbhip_api.hip writes them
+# the arrays of a record, in the order orbhip_search.hip writes them
 FIELDS = {1: ("kps", "desc", "u_right", "blocked", "bounds", "proj", "points", "pdesc", "fpar", "ipar", "feature_query"),
           2: ("kps", "desc", "u_right", "bounds", "inv_level_sigma2", "proj", "points", "pdesc", "ipar", "best_idx", "best_dist"),
           3: ("desc1", "kp1", "has_mp1", "stereo1", "fv1_node", "fv1_off", "fv1_feat", "desc2", "kp2", "has_mp2", "stereo2", "fv2_node", "fv2_off", "fv2_feat",

@@ -68,7 +68,7 @@ def run_case(rng, O, library=None):
 def run_single_image_sequence(rng, O, library=None, nframes=3):
     """What ORB_SLAM2 does, at a random geometry: one stereo pair at a time on two max_batch = 1 contexts, each pair followed by a random subset of
     the follow-ups (ComputeStereoMatches, a motion-model search, a local-map search) on the frame still in HBM - the frame epilogues of
-    orbhip_api.hip (row table / feature grid built behind the extraction once a context has seen the follow-up) at sizes nobody picked by hand."""
+    orbhip_host_path.hip (row table / feature grid built behind the extraction once a context has seen the follow-up) at sizes nobody picked by hand."""
     w, h = int(rng.integers(200, 800)), int(rng.integers(160, 520))
     n = int(rng.integers(150, 1800))
     sf, nl = float(rng.choice([1.2, 1.2, 1.3])), int(rng.integers(4, 9))

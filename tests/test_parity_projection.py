@@ -280,7 +280,7 @@ def test_stereo_columns_of_one_frame_leave_the_others_without(backend, oracle):
 def test_frame_epilogues_single_image_sequence(backend, oracle):
     """What ORB_SLAM2 does: one stereo pair at a time on two max_batch = 1 contexts, each pair followed by ComputeStereoMatches and two
     projection searches on the left frame.  From the second pair on the contexts build the right image's row table and the left image's 64x48
-    grid behind their own extractions (frame epilogues, orbhip_api.hip); every pair's results must equal the oracle's all the same, also when
+    grid behind their own extractions (frame epilogues, orbhip_host_path.hip); every pair's results must equal the oracle's all the same, also when
     the follow-ups change (a pair without any, a search without the stereo step)."""
     import sys, os
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

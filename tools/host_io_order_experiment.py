@@ -41,7 +41,7 @@ if "big" in mode:      # a large resident context like the bench's
         big.sync()
 if "closed" in mode:   # ... and destroyed again before the host path is measured
     big.close(); d.free(); big = None
-out = {"mode": mode, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "ORBHIP_STREAM_PRIO": os.environ.get("ORBHIP_STREAM_PRIO")}
+out = {"mode": mode, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")}
 if "fresh" in mode:
     for kind in ("pinned", "pageable", "pinned", "pageable"):
         ex = orb_slam2_amd.ORBextractor(2000, 1.2, 8, 20, 7, W, H, max_batch=Bh, blur_round_mode=1)

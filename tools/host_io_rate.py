@@ -76,5 +76,4 @@ for i in range(200):
 lat = (time.perf_counter() - t1) / 200
 best = {k: max(r["frames_per_s"] for r in rows if r["buffers"] == k) for k in ("pinned", "pageable")}
 print(json.dumps({"summary": True, "best_pinned_frames_per_s": best["pinned"], "best_pageable_frames_per_s": best["pageable"], "single_frame_latency_ms": round(lat * 1e3, 4),
-                  "copy_threads": os.environ.get("ORBHIP_COPY_THREADS", "default"),
                   "note": "extract only (no match), 1241x376 / 2000 features, H2D of images and D2H of key points + descriptors included"}))

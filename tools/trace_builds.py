@@ -98,7 +98,7 @@ def pjtrace():
     rep("    if (lane == 0 && wmatches) atomicAdd(&s_misc[PJM_NM], wmatches);", "    if (tid == 0) { const unsigned long long T2 = __builtin_amdgcn_s_memrealtime(); g_pj[0] += 1; g_pj[1] += c_steps; g_pj[2] += c_iter; g_pj[4] += T1 - T0; g_pj[5] += T2 - T1; g_pj[6] += J.nq; }\n    if (lane == 0 && wmatches) atomicAdd(&s_misc[PJM_NM], wmatches);")
 
 flags = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math".split()
-allobjs = "orbhip_api.o orbhip_kernels_extract.o orbhip_kernels_match.o orbhip_kernels_stereo.o orbhip_kernels_proj.o orbhip_kernels_geom.o orbhip_bow.o orbhip_pool.o".split()
+allobjs = "orbhip_api.o orbhip_host_path.o orbhip_search.o orbhip_frame.o orbhip_kernels_extract.o orbhip_kernels_match.o orbhip_kernels_stereo.o orbhip_kernels_proj.o orbhip_kernels_geom.o orbhip_bow.o orbhip_pool.o".split()
 for name in sys.argv[1:] or ["qttrace"]:
     proj = name == "pjtrace"
     s = SRC_PROJ if proj else SRC
