@@ -413,6 +413,44 @@ orbhip_status orbhip_search_for_triangulation_batch(int device, const orbhip_tri
 double orbhip_voc_score(const orbhip_voc* voc, const uint32_t* id1, const double* val1, int n1,
                         const uint32_t* id2, const double* val2, int n2);
 
+/* -------- key-frame database (KeyFrameDatabase.cc) ------------------------------------------------------
+   The loop and relocalisation queries of ORB_SLAM2::KeyFrameDatabase on a device-resident store of the key frames' BowVectors.  A key frame is
+   a SLOT (orbhip_kfdb_add hands it out, orbhip_kfdb_erase frees it for reuse); per slot and query kind the database holds what the reference
+   keeps in the KeyFrame: {query, words, score} = mnRelocQuery / mnRelocWords / mRelocScore and mnLoopQuery / mnLoopWords / mLoopScore, all 0 for
+   a new key frame.  Only scoring 0 (L1_NORM, what ORBvoc.txt declares) is supported: orbhip_kfdb_create returns
+   ORBHIP_ERR_UNSUPPORTED for the others.  A BowVector has at most 8192 words, ids ascending and below nwords.  Every entry is synchronous, takes
+   host pointers, runs on the calling thread's own stream (orbhip_kfdb_query_frame: the extractor's) and holds the database's one lock, as the
+   reference's members hold mMutex: add, erase and both queries may be called from different threads at once. */
+typedef struct orbhip_kfdb orbhip_kfdb;
+enum { ORBHIP_KFDB_RELOC = 0, ORBHIP_KFDB_LOOP = 1 };
+typedef struct { int32_t slot; int32_t words; float score; } orbhip_kfdb_hit;     /* a scored key frame: mnRelocWords / mnLoopWords and (float)score */
+orbhip_status orbhip_kfdb_create(orbhip_kfdb** out, int device, int nwords /* ORBVocabulary::size() */, int scoring);
+void orbhip_kfdb_destroy(orbhip_kfdb* db);
+orbhip_status orbhip_kfdb_clear(orbhip_kfdb* db);                     /* every slot is freed */
+int orbhip_kfdb_size(orbhip_kfdb* db);                                /* key frames held */
+orbhip_status orbhip_kfdb_add(orbhip_kfdb* db, const uint32_t* bow_id, const double* bow_val, int nbow, int* slot);
+orbhip_status orbhip_kfdb_erase(orbhip_kfdb* db, int slot);
+/* The first half of DetectRelocalizationCandidates (KeyFrameDatabase.cc:199-256, kind RELOC) / DetectLoopCandidates (:76-142, kind LOOP) for the
+   BowVector (bow_id, bow_val) and the query id `qid` (Frame::mnId / KeyFrame::mnId).  excluded_slots (LOOP only) = the key frames connected to the
+   querying key frame (GetConnectedKeyFrames); min_score (LOOP only) = minScore.  hits[0 .. *nhits) = lScoreAndMatch in the reference's order,
+   *nsharing = lKFsSharingWords.size(), *min_common = minCommonWords (0 when nothing shares a word).  With more than `cap` hits the first `cap` are
+   written, *nhits says how many there are and the call returns ORBHIP_ERR_CAPACITY; the key frames' state is that of the completed query. */
+orbhip_status orbhip_kfdb_query(orbhip_kfdb* db, int kind, uint64_t qid, const uint32_t* bow_id, const double* bow_val, int nbow,
+                                const int32_t* excluded_slots, int nexcluded, float min_score,
+                                orbhip_kfdb_hit* hits, int cap, int* nhits, int* nsharing, int* min_common);
+/* ... with the BowVector read where orbhip_compute_bow(ctx, voc, ...) left it for `frame`: nothing of it travels */
+orbhip_status orbhip_kfdb_query_frame(orbhip_kfdb* db, int kind, uint64_t qid, orbhip_ctx* ctx, orbhip_voc* voc, int frame,
+                                      const int32_t* excluded_slots, int nexcluded, float min_score,
+                                      orbhip_kfdb_hit* hits, int cap, int* nhits, int* nsharing, int* min_common);
+orbhip_status orbhip_kfdb_state(orbhip_kfdb* db, int kind, int slot, uint64_t* query, int* words, float* score);
+/* mpVoc->score(bow, key frame) for n named key frames in one launch (LoopClosing.cc:123-139); scoring as L1Scoring::score, double for double */
+orbhip_status orbhip_kfdb_scores(orbhip_kfdb* db, const uint32_t* bow_id, const double* bow_val, int nbow, const int32_t* slots, int n, double* scores);
+/* The second half (:144-196 LOOP, :258-308 RELOC), host arithmetic over the state the query left: hit i's neighbours
+   neigh_slot[neigh_off[i] .. neigh_off[i+1]) = GetBestCovisibilityKeyFrames(10) of its key frame (a slot that holds no key frame is skipped).
+   out_slots = vpLoopCandidates / vpRelocCandidates. */
+orbhip_status orbhip_kfdb_select(orbhip_kfdb* db, int kind, uint64_t qid, int min_common, float min_score, const orbhip_kfdb_hit* hits, int nhits,
+                                 const int32_t* neigh_off, const int32_t* neigh_slot, int32_t* out_slots, int cap, int* nout);
+
 /* -------- distorted cameras and rectification -------------------------------------------
    Monocular / RGB-D cameras with lens distortion (TUM1-3.yaml): Frame's constructors call UndistortKeyPoints (Frame.cc:404-434)
    and, once, ComputeImageBounds (Frame.cc:436-464); the 64x48 grid and every windowed search then work on mvKeysUn inside the

@@ -8,6 +8,8 @@
     ... --resident-bow           optional (with this repository's ORBVocabulary class in place, step 3e): Frame::ComputeBoW reads the descriptors in HBM
     ... --flat-frustum           optional: Frame::isInFrustum forwards to ORBmatcher::IsInFrustum (flat floats, the map point visited once, no cv::Mat temporaries)
     ... --skip-host-grid         optional: Frame::AssignFeaturesToGrid does nothing - with this repository's ORBmatcher.cc nobody reads the host's 64 x 48 grid
+    ... --keyframe-database      optional: include/KeyFrameDatabase.h + src/KeyFrameDatabase.cc become this repository's class on the device key-frame database
+                                 (orbhip_kfdb_*): DetectLoopCandidates / DetectRelocalizationCandidates as one device query each
 
 What it produces (nothing else of the checkout changes; Tracking.cc, LocalMapping.cc, LoopClosing.cc, KeyFrame*.cc, MapPoint.cc compile as they are):
   REPLACED by this repository's files (an installer's copy, no text surgery):
@@ -185,7 +187,8 @@ def main():
     drgbd = "--device-rgbd" in argv
     nogrid = "--skip-host-grid" in argv
     flat = "--flat-frustum" in argv
-    argv = [a for a in argv if a not in ("--stereo-one-call", "--resident-bow", "--device-rgbd", "--skip-host-grid", "--flat-frustum")]
+    kfdb = "--keyframe-database" in argv
+    argv = [a for a in argv if a not in ("--stereo-one-call", "--resident-bow", "--device-rgbd", "--skip-host-grid", "--flat-frustum", "--keyframe-database")]
     emit_patch = bool(argv) and argv[0] == "--patch"
     if emit_patch:
         argv = argv[1:]
@@ -197,6 +200,8 @@ def main():
     copies = {"include/ORBextractor.h": "include/ORBextractor.h", "src/ORBextractor.cc": "orb_slam2_amd/cpp/ORBextractor.cc", "include/orbhip.h": "include/orbhip.h",
               "include/ORBmatcher.h": "include/ORBmatcher.h", "src/ORBmatcher.cc": "orb_slam2_amd/cpp/ORBmatcher.cc", "include/ORBmatcherBatch.h": "include/ORBmatcherBatch.h",
               "include/orbhip_gemm_probe.h": "include/orbhip_gemm_probe.h"}
+    if kfdb:
+        copies.update({"include/KeyFrameDatabase.h": "include/KeyFrameDatabase.h", "src/KeyFrameDatabase.cc": "orb_slam2_amd/cpp/KeyFrameDatabase.cc"})
     if emit_patch:
         for rel, new in edited.items():
             old = open(os.path.join(ref, rel)).read()

@@ -1,0 +1,125 @@
+// KeyFrameDatabase.cc — ORB_SLAM2::KeyFrameDatabase on liborbhip.so (see include/KeyFrameDatabase.h).  The reference's inverted file and its walks are
+// replaced by the device key-frame database of include/orbhip.h: both queries are gather -> ONE device call (orbhip_kfdb_query: the shared-word scan,
+// the scores, the hit list in the reference's order) -> GetBestCovisibilityKeyFrames(10) per hit -> orbhip_kfdb_select (the covisibility accumulation).
+#include "KeyFrameDatabase.h"
+#include "ORBextractor.h"
+#include "orbhip.h"
+#include <string>
+
+namespace ORB_SLAM2
+{
+
+static void orbhip_check(orbhip_status st, const char* what)
+{
+    if (st != ORBHIP_OK) throw ORBhipError(std::string("KeyFrameDatabase::") + what + ": " + orbhip_last_error());
+}
+
+static void FlattenBow(const DBoW2::BowVector &bow, std::vector<uint32_t> &id, std::vector<double> &val)
+{
+    id.clear(); val.clear(); id.reserve(bow.size()); val.reserve(bow.size());
+    for (DBoW2::BowVector::const_iterator it = bow.begin(); it != bow.end(); ++it) { id.push_back(it->first); val.push_back(it->second); }
+}
+
+// ORB_SLAM2's vocabularies (ORBvoc.txt) declare L1_NORM, scoring 0: the one the device database scores with
+KeyFrameDatabase::KeyFrameDatabase(const ORBVocabulary &voc) : mpVoc(&voc), mpDb(NULL)
+{
+    int device = 0;
+    if (const char* dev = getenv("ORBHIP_DEVICE")) device = atoi(dev);
+    orbhip_check(orbhip_kfdb_create(&mpDb, device, (int)voc.size(), 0), "KeyFrameDatabase");
+}
+
+KeyFrameDatabase::~KeyFrameDatabase() { if (mpDb) orbhip_kfdb_destroy(mpDb); }
+
+void KeyFrameDatabase::add(KeyFrame *pKF)
+{
+    std::vector<uint32_t> id; std::vector<double> val;
+    FlattenBow(pKF->mBowVec, id, val);
+    std::unique_lock<std::mutex> lock(mMutex);
+    int slot = -1;
+    orbhip_check(orbhip_kfdb_add(mpDb, id.empty() ? NULL : &id[0], val.empty() ? NULL : &val[0], (int)id.size(), &slot), "add");
+    if ((size_t)slot >= mvpKeyFrameOf.size()) mvpKeyFrameOf.resize((size_t)slot + 1, static_cast<KeyFrame*>(NULL));
+    mvpKeyFrameOf[slot] = pKF;
+    mSlotOf[pKF] = slot;
+}
+
+void KeyFrameDatabase::erase(KeyFrame* pKF)
+{
+    std::unique_lock<std::mutex> lock(mMutex);
+    std::map<KeyFrame*, int>::iterator it = mSlotOf.find(pKF);
+    if (it == mSlotOf.end()) return;                                  // (the reference's erase of an unknown key frame finds nothing in any list)
+    orbhip_check(orbhip_kfdb_erase(mpDb, it->second), "erase");
+    mvpKeyFrameOf[it->second] = NULL;
+    mSlotOf.erase(it);
+}
+
+void KeyFrameDatabase::clear()
+{
+    std::unique_lock<std::mutex> lock(mMutex);
+    orbhip_check(orbhip_kfdb_clear(mpDb), "clear");
+    mSlotOf.clear(); mvpKeyFrameOf.clear();
+}
+
+std::vector<KeyFrame*> KeyFrameDatabase::Detect(int kind, unsigned long long qid, const DBoW2::BowVector &bow, const std::set<KeyFrame*> &sConnected, float minScore)
+{
+    std::vector<uint32_t> id; std::vector<double> val;
+    FlattenBow(bow, id, val);
+    std::vector<int32_t> vExcluded; int nCap = 0;
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        for (std::set<KeyFrame*>::const_iterator sit = sConnected.begin(); sit != sConnected.end(); ++sit) {
+            std::map<KeyFrame*, int>::const_iterator it = mSlotOf.find(*sit);
+            if (it != mSlotOf.end()) vExcluded.push_back(it->second);
+        }
+        nCap = (int)mSlotOf.size();
+    }
+    std::vector<orbhip_kfdb_hit> vHits((size_t)nCap + 1);
+    int nHits = 0, nSharing = 0, nMinCommon = 0;
+    orbhip_status st = orbhip_kfdb_query(mpDb, kind, qid, id.empty() ? NULL : &id[0], val.empty() ? NULL : &val[0], (int)id.size(),
+                                         vExcluded.empty() ? NULL : &vExcluded[0], (int)vExcluded.size(), minScore, &vHits[0], (int)vHits.size(), &nHits, &nSharing, &nMinCommon);
+    if (st == ORBHIP_ERR_CAPACITY) nHits = (int)vHits.size();       // key frames were added since the count was taken: the first ones in the reference's order are kept
+    else orbhip_check(st, "query");
+    if (nHits == 0) return std::vector<KeyFrame*>();
+
+    // the hits' key frames (under the mapping's lock), then their best covisibles (under the key frames' own mutexes), then the neighbours' slots
+    std::vector<KeyFrame*> vpHit((size_t)nHits, static_cast<KeyFrame*>(NULL));
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        for (int i = 0; i < nHits; i++) if ((size_t)vHits[i].slot < mvpKeyFrameOf.size()) vpHit[i] = mvpKeyFrameOf[vHits[i].slot];
+    }
+    std::vector<std::vector<KeyFrame*> > vvpNeighs((size_t)nHits);
+    for (int i = 0; i < nHits; i++) if (vpHit[i]) vvpNeighs[i] = vpHit[i]->GetBestCovisibilityKeyFrames(10);
+    std::vector<int32_t> vOff((size_t)nHits + 1, 0), vNeighSlot;
+    std::vector<KeyFrame*> vpOut;
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        for (int i = 0; i < nHits; i++) {
+            for (size_t j = 0; j < vvpNeighs[i].size(); j++) {
+                std::map<KeyFrame*, int>::const_iterator it = mSlotOf.find(vvpNeighs[i][j]);
+                vNeighSlot.push_back(it != mSlotOf.end() ? it->second : -1);
+            }
+            vOff[i + 1] = (int32_t)vNeighSlot.size();
+        }
+    }
+    std::vector<int32_t> vOutSlot((size_t)nHits + 1);
+    int nOut = 0;
+    orbhip_check(orbhip_kfdb_select(mpDb, kind, qid, nMinCommon, minScore, &vHits[0], nHits, &vOff[0], vNeighSlot.empty() ? NULL : &vNeighSlot[0],
+                                    &vOutSlot[0], (int)vOutSlot.size(), &nOut), "select");
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        vpOut.reserve((size_t)nOut);
+        for (int i = 0; i < nOut; i++) if ((size_t)vOutSlot[i] < mvpKeyFrameOf.size() && mvpKeyFrameOf[vOutSlot[i]]) vpOut.push_back(mvpKeyFrameOf[vOutSlot[i]]);
+    }
+    return vpOut;
+}
+
+std::vector<KeyFrame*> KeyFrameDatabase::DetectLoopCandidates(KeyFrame* pKF, float minScore)
+{
+    return Detect(ORBHIP_KFDB_LOOP, pKF->mnId, pKF->mBowVec, pKF->GetConnectedKeyFrames(), minScore);
+}
+
+std::vector<KeyFrame*> KeyFrameDatabase::DetectRelocalizationCandidates(Frame *F)
+{
+    return Detect(ORBHIP_KFDB_RELOC, F->mnId, F->mBowVec, std::set<KeyFrame*>(), 0.0f);
+}
+
+} //namespace ORB_SLAM

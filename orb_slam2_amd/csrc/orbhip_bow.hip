@@ -998,6 +998,19 @@ extern "C" orbhip_status orbhip_fetch_bow(orbhip_ctx* ctx, orbhip_voc* v, int fr
     return voc_fetch(w, frame, s, bow_id, bow_val, nbow, fv_node, fv_off, fv_feat, nfv);
 }
 
+orbhip_status orbhip_bow_resident(orbhip_ctx* ctx, orbhip_voc* v, int frame, const uint32_t** d_id, const double** d_val, const int** d_nbow, int* cap, int* device, int* nwords, hipStream_t* s)
+{
+    BowWs* w = nullptr;
+    { std::lock_guard<std::mutex> lock(v->m); auto it = v->per_ctx.find(ctx); if (it != v->per_ctx.end()) w = &it->second; }
+    if (!w || frame < 0 || frame >= w->last_frames) return orbhip_set_error(ORBHIP_ERR_INVALID, "frame %d outside the %d frames of this extractor's last orbhip_compute_bow", frame, w ? w->last_frames : 0);
+    const uint8_t* d_desc = nullptr; const int* d_n = nullptr; int ocap = 0, last = 0;
+    orbhip_internal_outputs(ctx, &d_desc, &d_n, &ocap, &last, device, s);
+    const uint8_t* block = w->d_out + (size_t)frame * (size_t)w->out.stride;
+    *d_val = reinterpret_cast<const double*>(block); *d_id = reinterpret_cast<const uint32_t*>(block + w->out.o_id); *d_nbow = reinterpret_cast<const int*>(block + w->out.o_cnt);
+    *cap = w->cap; *nwords = v->nwords;
+    return ORBHIP_OK;
+}
+
 // TemplatedVocabulary::score -> the scoring object selected by the file header (ScoringObject.cpp:24-313); two ascending
 // (id, value) arrays.  A few thousand flops on the host: not worth a launch.
 extern "C" double orbhip_voc_score(const orbhip_voc* v, const uint32_t* id1, const double* val1, int n1, const uint32_t* id2, const double* val2, int n2)

@@ -1,0 +1,533 @@
+// orbhip_kfdb.hip — KeyFrameDatabase on the device: the loop and relocalisation queries of ORB_SLAM2 (src/KeyFrameDatabase.cc) as a forward scan.
+//
+// The reference keeps an inverted file (one std::list<KeyFrame*> per word) and walks the lists of the query's words.  What that walk produces is a
+// function of three things per key frame: how many words it shares with the query, which shared word comes first, and when it was added (words are
+// visited ascending, each list is in add order and erase() keeps it).  So no list exists here.  The store is a forward store: every key frame's
+// BowVector lies as one range of a word-id arena (u32) and a weight arena (f64); a query is
+//   k_kfdb_scan    one wavefront per key frame: its words are looked up in the query's sorted id list (LDS, bisection) -> shared-word count, first
+//                  shared word and the L1 score, bit for bit L1Scoring::score (ScoringObject.cpp:23-68): the terms in ascending word order in ONE
+//                  dependent f64 chain from 0
+//   k_kfdb_select  one workgroup: the per-key-frame state rule of KeyFrameDatabase.cc:86-104 / :207-222 (mnRelocQuery, mnRelocWords, mRelocScore and
+//                  the mnLoop* fields live here, per slot and kind), maxCommonWords, minCommonWords = (int)(max * 0.8f), the compaction of the key frames
+//                  above it, their order (first shared word << 32 | add sequence) and the hit list (lScoreAndMatch)
+// The covisibility accumulation (:144-196, :258-308) needs the caller's neighbour lists and is host arithmetic (orbhip_kfdb_select).
+// One lock per database, held for a whole entry: the reference's mMutex (add from LocalMapping, the queries from LoopClosing and Tracking).
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <utility>
+#include <vector>
+#include <algorithm>
+#include "../../include/orbhip.h"
+#include "orbhip_internal.h"
+
+#define KFCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return orbhip_set_error(ORBHIP_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+#define KFDB_MAX_WORDS 8192            // BOW_MAX_FEATURES (orbhip_bow.hip): a BowVector has at most one word per feature
+
+struct KfSlot { unsigned long long off; unsigned n, seq, live, pad; };      // range [off, off + n) of both arenas, add sequence number, live flag
+struct KfState { unsigned long long query; int words; float score; };       // mnRelocQuery / mnRelocWords / mRelocScore (or the mnLoop* fields) of one key frame
+
+// ------------------------------------------------------------------------------------------------ k_kfdb_scan
+struct KfScanParams {
+    const uint32_t* ids; const double* vals; const KfSlot* slots;
+    const int* list; int n;                                  // wave w scans slot list[w] (list == nullptr: slot w), n waves in all
+    const uint32_t* q_id; const double* q_val;               // the query's BowVector, ascending ids
+    const int* q_n_dev; int q_n, q_cap;                      // its length: read on the device (a resident frame's nbow) or given; q_cap entries of LDS
+    int* cnt; uint32_t* first; double* score;                // per wave: shared words, first shared word, score
+};
+
+__device__ __forceinline__ double kf_readlane(double v, int lane)             // lane is wave-uniform: two v_readlane_b32
+{
+    int h[2]; memcpy(h, &v, 8);
+    h[0] = __builtin_amdgcn_readlane(h[0], lane); h[1] = __builtin_amdgcn_readlane(h[1], lane);
+    double r; memcpy(&r, h, 8); return r;
+}
+
+#define KS_T 256                       // four wavefronts share one staged copy of the query's ids
+__global__ __launch_bounds__(KS_T) void k_kfdb_scan(KfScanParams P)
+{
+    HIP_DYNAMIC_SHARED(uint32_t, q)
+    const int tid = threadIdx.x, lane = tid & 63;
+    int nq = P.q_n_dev ? *P.q_n_dev : P.q_n;
+    nq = nq < 0 ? 0 : nq > P.q_cap ? P.q_cap : nq;
+    for (int i = tid; i < nq; i += KS_T) q[i] = P.q_id[i];
+    __syncthreads();
+    const int w = blockIdx.x * (KS_T / 64) + (tid >> 6);
+    if (w >= P.n) return;                                                     // (whole waves, after the kernel's only barrier)
+    const KfSlot S = P.slots[P.list ? P.list[w] : w];
+    int top = 0;                                                              // largest power of two <= nq: the bisection's first step
+    if (nq > 0) top = 1 << (31 - __clz(nq));
+    int cnt = 0; uint32_t first = 0xffffffffu; double s = 0.0;
+    if (S.live && nq > 0 && S.n > 0) {
+        const uint32_t* kid = P.ids + S.off; const double* kval = P.vals + S.off;
+        uint32_t id_next = (unsigned)lane < S.n ? kid[lane] : 0xffffffffu;
+        for (unsigned base = 0; base < S.n; base += 64) {
+            const unsigned i = base + lane; const bool in = i < S.n;
+            const uint32_t id = id_next;
+            id_next = i + 64 < S.n ? kid[i + 64] : 0xffffffffu;               // the next chunk's ids are on their way while this one is searched
+            int pos = 0;                                                      // number of query ids below `id` (lower bound), the same steps in every lane
+            for (int st = top; st; st >>= 1) { const int p = pos + st; if (p <= nq && q[p - 1] < id) pos = p; }
+            const bool hit = in && pos < nq && q[pos] == id;
+            double term = 0.0;
+            if (hit) {                                                        // score(query, key frame): vi the query's weight, wi the key frame's; both loads leave together
+                const double wi = kval[i], vi = P.q_val[pos];
+                term = __dsub_rn(__dsub_rn(fabs(__dsub_rn(vi, wi)), fabs(vi)), fabs(wi));
+            }
+            unsigned long long m = __ballot(hit);
+            if (m) {
+                if (cnt == 0) first = (uint32_t)__builtin_amdgcn_readlane((int)id, __ffsll((long long)m) - 1);
+                cnt += __popcll(m);
+                // the shared pairs of this chunk in word order (the set bits ascending), added to the ONE chain that runs through every chunk of the key frame
+                while (m) { const int l = __ffsll((long long)m) - 1; m &= m - 1; s = __dadd_rn(s, kf_readlane(term, l)); }
+            }
+        }
+    }
+    if (lane == 0) { P.cnt[w] = cnt; P.first[w] = first; P.score[w] = -s / 2.0; }
+}
+
+// ------------------------------------------------------------------------------------------------ k_kfdb_select
+struct KfSelectParams {
+    const KfSlot* slots; KfState* state; int nslots;         // state: this kind's
+    const int* cnt; const uint32_t* first; const double* score;      // k_kfdb_scan's answers, per slot
+    const int* excl; int nexcl;                              // LOOP: the slots connected to the querying key frame, ascending
+    int kind; unsigned long long qid; float min_score;
+    int* flag;                                               // [nslots] words of a listed key frame, 0 otherwise
+    unsigned long long* keys; int* pay; int cap2;            // sort workspace for more than KSEL_LDS listed key frames, cap2 a power of two >= nslots
+    orbhip_kfdb_hit* hits; int* meta;                        // hit list in the reference's order; meta = {nhits, nsharing, min_common}
+};
+
+#define KSEL_T 1024                    // slots per pass
+#define KSEL_LDS 4096                  // listed key frames whose sort fits the LDS (12 bytes each)
+
+// bitonic sort of n2 (a power of two) unique keys with a payload, by the whole workgroup
+template <typename KP, typename PP> __device__ __forceinline__ void kf_bitonic(KP keys, PP pay, int n2, int tid)
+{
+    for (int k = 2; k <= n2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (n2 >> 1); t += KSEL_T) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long a = keys[i], b = keys[l];
+                if ((a > b) == ((i & k) == 0) && a != b) { keys[i] = b; keys[l] = a; const int pa = pay[i]; pay[i] = pay[l]; pay[l] = pa; }
+            }
+            __syncthreads();
+        }
+}
+
+__global__ __launch_bounds__(KSEL_T) void k_kfdb_select(KfSelectParams P)
+{
+    __shared__ int s_max, s_nlist, s_nhit;
+    __shared__ unsigned long long s_key[KSEL_LDS];
+    __shared__ int s_pay[KSEL_LDS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) { s_max = 0; s_nlist = 0; s_nhit = 0; }
+    __syncthreads();
+    // pass 1: the state rule; a slot is one thread's alone
+    int lmax = 0, nl = 0;
+    for (int b = 0; b < P.nslots; b += KSEL_T) {
+        const int i = b + tid;
+        if (i >= P.nslots) break;
+        int listed = 0;
+        const int c = P.slots[i].live ? P.cnt[i] : 0;
+        if (c >= 1) {
+            KfState st = P.state[i];
+            if (st.query == P.qid) st.words += c;                                                 // met before under this query id: counts on, not listed again
+            else {
+                bool excluded = false;
+                if (P.kind == ORBHIP_KFDB_LOOP && P.nexcl > 0) {
+                    int lo = 0, hi = P.nexcl;
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (P.excl[mid] < i) lo = mid + 1; else hi = mid; }
+                    excluded = lo < P.nexcl && P.excl[lo] == i;
+                }
+                if (excluded) st.words = 1;                                                       // every shared word resets the count to 0 and adds one
+                else { st.query = P.qid; st.words = c; listed = c; }
+            }
+            P.state[i].query = st.query; P.state[i].words = st.words;
+        }
+        P.flag[i] = listed;
+        lmax = max(lmax, listed); nl += listed != 0;
+    }
+    for (int o = 32; o; o >>= 1) { lmax = max(lmax, __shfl_xor(lmax, o)); nl += __shfl_xor(nl, o); }
+    if (lane == 0 && nl) { atomicMax(&s_max, lmax); atomicAdd(&s_nlist, nl); }
+    __syncthreads();
+    const int nlist = s_nlist;
+    const int minc = (int)__fmul_rn((float)s_max, 0.8f);                                          // int minCommonWords = maxCommonWords*0.8f;
+    const bool in_lds = nlist <= KSEL_LDS;
+    // pass 2: score and compact the listed key frames above minCommonWords (any order: they are sorted next)
+    for (int b = 0; b < P.nslots; b += KSEL_T) {                                                  // (whole waves leave together: KSEL_T is a multiple of 64)
+        const int i = b + tid;
+        bool hit = false; unsigned long long key = 0;
+        if (i < P.nslots && P.flag[i] > minc) {
+            const float sf = (float)P.score[i];
+            P.state[i].score = sf;                                                                // written for every scored key frame ...
+            hit = P.kind == ORBHIP_KFDB_RELOC || sf >= P.min_score;                               // ... listed only above minScore (LOOP)
+            key = ((unsigned long long)P.first[i] << 32) | P.slots[i].seq;
+        }
+        const unsigned long long m = __ballot(hit);
+        if (m) {
+            const int leader = __ffsll((long long)m) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&s_nhit, (int)__popcll(m));                      // one LDS atomic per wave
+            base = __builtin_amdgcn_readlane(base, leader);
+            const int pos = base + (int)__popcll(m & ((1ull << lane) - 1ull));
+            if (hit) { if (in_lds) { s_key[pos] = key; s_pay[pos] = i; } else { P.keys[pos] = key; P.pay[pos] = i; } }
+        }
+    }
+    __syncthreads();
+    const int n = s_nhit;
+    int n2 = 1; while (n2 < n) n2 <<= 1;
+    if (in_lds) {
+        for (int t = n + tid; t < n2; t += KSEL_T) { s_key[t] = ~0ull; s_pay[t] = 0; }
+        __syncthreads();
+        kf_bitonic(s_key, s_pay, n2, tid);
+        for (int t = tid; t < n; t += KSEL_T) { const int slot = s_pay[t]; orbhip_kfdb_hit h; h.slot = slot; h.words = P.flag[slot]; h.score = (float)P.score[slot]; P.hits[t] = h; }
+    } else {
+        for (int t = n + tid; t < n2; t += KSEL_T) { P.keys[t] = ~0ull; P.pay[t] = 0; }
+        __syncthreads();
+        kf_bitonic(P.keys, P.pay, n2, tid);
+        for (int t = tid; t < n; t += KSEL_T) { const int slot = P.pay[t]; orbhip_kfdb_hit h; h.slot = slot; h.words = P.flag[slot]; h.score = (float)P.score[slot]; P.hits[t] = h; }
+    }
+    if (tid == 0) { P.meta[0] = n; P.meta[1] = nlist; P.meta[2] = nlist ? minc : 0; }
+}
+
+// the state of the named slots (list[i] < 0: zeros), for orbhip_kfdb_select's neighbour lists
+__global__ __launch_bounds__(256) void k_kfdb_gather(const KfState* state, const int* list, int n, KfState* out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int slot = list[i];
+    unsigned long long query = 0; int words = 0; float score = 0.0f;
+    if (slot >= 0) { query = state[slot].query; words = state[slot].words; score = state[slot].score; }
+    out[i].query = query; out[i].words = words; out[i].score = score;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+struct orbhip_kfdb {
+    int device = 0, nwords = 0;
+    std::mutex m;
+    // forward store: both arenas grow together by doubling; erased ranges are reused first-fit
+    uint32_t* d_ids = nullptr; double* d_vals = nullptr; size_t arena_cap = 0, arena_end = 0;
+    std::vector<std::pair<size_t, size_t>> holes;            // (offset, length)
+    KfSlot* d_slots = nullptr; KfState* d_state[2] = {nullptr, nullptr}; int slot_cap = 0, nslots = 0, nlive = 0; unsigned next_seq = 0;      // slot_cap: a power of two
+    std::vector<KfSlot> h_slots; std::vector<int> free_slots;
+    // per-query workspace (sized with the slot arrays), the query's BowVector, slot lists
+    int* d_cnt = nullptr; uint32_t* d_first = nullptr; double* d_score = nullptr; int* d_flag = nullptr; unsigned long long* d_keys = nullptr; int* d_pay = nullptr;
+    orbhip_kfdb_hit* d_hits = nullptr; int* d_meta = nullptr; uint32_t* d_qid = nullptr; double* d_qval = nullptr;
+    int* d_list = nullptr; size_t list_cap = 0; KfState* d_gather = nullptr; size_t gather_cap = 0;
+};
+
+static void kf_free(void* p) { if (p) (void)hipFree(p); }
+template <typename T> static hipError_t kf_grow(T** p, size_t* cap, size_t need)      // contents are not kept
+{
+    if (need <= *cap) return hipSuccess;
+    kf_free(*p); *p = nullptr; *cap = 0;
+    const size_t nc = std::max<size_t>(need + need / 2, 256);
+    const hipError_t e = orbhip_dmalloc((void**)p, nc * sizeof(T));
+    if (e == hipSuccess) *cap = nc;
+    return e;
+}
+// a larger array with the first `keep` elements of the old one (the caller has drained every stream that used it: all entries are synchronous)
+template <typename T> static hipError_t kf_regrow(T** p, size_t keep, size_t ncap)
+{
+    T* np = nullptr;
+    hipError_t e = orbhip_dmalloc((void**)&np, std::max<size_t>(ncap, 1) * sizeof(T)); if (e != hipSuccess) return e;
+    if (keep && *p) { e = hipMemcpy(np, *p, keep * sizeof(T), hipMemcpyDeviceToDevice); if (e != hipSuccess) { (void)hipFree(np); return e; } }
+    kf_free(*p); *p = np;
+    return hipSuccess;
+}
+
+static orbhip_status kf_ensure_slots(orbhip_kfdb* db, int need)
+{
+    if (need <= db->slot_cap) return ORBHIP_OK;
+    int nc = std::max(db->slot_cap, 64); while (nc < need) nc *= 2;
+    const size_t keep = (size_t)db->nslots, C = (size_t)nc;
+    KFCHK(kf_regrow(&db->d_slots, keep, C)); KFCHK(kf_regrow(&db->d_state[0], keep, C)); KFCHK(kf_regrow(&db->d_state[1], keep, C));
+    KFCHK(kf_regrow(&db->d_cnt, 0, C)); KFCHK(kf_regrow(&db->d_first, 0, C)); KFCHK(kf_regrow(&db->d_score, 0, C)); KFCHK(kf_regrow(&db->d_flag, 0, C));
+    KFCHK(kf_regrow(&db->d_keys, 0, C)); KFCHK(kf_regrow(&db->d_pay, 0, C)); KFCHK(kf_regrow(&db->d_hits, 0, C));
+    db->slot_cap = nc;
+    return ORBHIP_OK;
+}
+
+static bool kf_ascending(const uint32_t* id, int n, int nwords)
+{
+    for (int i = 0; i < n; i++) if (id[i] >= (uint32_t)nwords || (i && id[i] <= id[i - 1])) return false;
+    return true;
+}
+
+extern "C" orbhip_status orbhip_kfdb_create(orbhip_kfdb** out, int device, int nwords, int scoring)
+{
+    if (!out || nwords < 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    if (scoring != 0) return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "key-frame database: scoring %d (only 0, L1_NORM, runs on the device: it is what ORBvoc.txt declares, and KL needs a log with no bit-exact device form)", scoring);
+    KFCHK(hipSetDevice(device));
+    orbhip_kfdb* db = new orbhip_kfdb(); db->device = device; db->nwords = nwords;
+    hipError_t e = orbhip_dmalloc((void**)&db->d_meta, 4 * sizeof(int));
+    if (e == hipSuccess) e = orbhip_dmalloc((void**)&db->d_qid, KFDB_MAX_WORDS * sizeof(uint32_t));
+    if (e == hipSuccess) e = orbhip_dmalloc((void**)&db->d_qval, KFDB_MAX_WORDS * sizeof(double));
+    if (e != hipSuccess) { orbhip_kfdb_destroy(db); return orbhip_set_error(ORBHIP_ERR_HIP, "key-frame database: %s", hipGetErrorString(e)); }
+    *out = db;
+    return ORBHIP_OK;
+}
+
+extern "C" void orbhip_kfdb_destroy(orbhip_kfdb* db)
+{
+    if (!db) return;
+    (void)hipSetDevice(db->device);
+    void* ptrs[] = {db->d_ids, db->d_vals, db->d_slots, db->d_state[0], db->d_state[1], db->d_cnt, db->d_first, db->d_score, db->d_flag, db->d_keys, db->d_pay, db->d_hits,
+                    db->d_meta, db->d_qid, db->d_qval, db->d_list, db->d_gather};
+    for (void* p : ptrs) kf_free(p);
+    delete db;
+}
+
+extern "C" orbhip_status orbhip_kfdb_clear(orbhip_kfdb* db)
+{
+    if (!db) return orbhip_set_error(ORBHIP_ERR_INVALID, "null database");
+    std::lock_guard<std::mutex> lock(db->m);
+    db->nslots = 0; db->nlive = 0; db->arena_end = 0; db->holes.clear(); db->h_slots.clear(); db->free_slots.clear();
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_kfdb_size(orbhip_kfdb* db)
+{
+    if (!db) return 0;
+    std::lock_guard<std::mutex> lock(db->m);
+    return db->nlive;
+}
+
+extern "C" orbhip_status orbhip_kfdb_add(orbhip_kfdb* db, const uint32_t* bow_id, const double* bow_val, int nbow, int* slot_out)
+{
+    OrbApiTimer api_timer;
+    if (!db || !slot_out || nbow < 0 || (nbow > 0 && (!bow_id || !bow_val))) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    *slot_out = -1;
+    if (nbow > KFDB_MAX_WORDS) return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "a BowVector of %d words (at most %d)", nbow, KFDB_MAX_WORDS);
+    if (!kf_ascending(bow_id, nbow, db->nwords)) return orbhip_set_error(ORBHIP_ERR_INVALID, "BowVector ids must ascend and lie below %d", db->nwords);
+    std::lock_guard<std::mutex> lock(db->m);
+    KFCHK(hipSetDevice(db->device));
+    hipStream_t s = orbhip_thread_stream(db->device);
+    // a range of the arenas: an erased one that is large enough, else the end
+    size_t off = db->arena_end; bool from_hole = false;
+    for (size_t h = 0; h < db->holes.size() && nbow > 0; h++)
+        if (db->holes[h].second >= (size_t)nbow) {
+            off = db->holes[h].first; from_hole = true;
+            if (db->holes[h].second == (size_t)nbow) db->holes.erase(db->holes.begin() + h); else { db->holes[h].first += nbow; db->holes[h].second -= nbow; }
+            break;
+        }
+    if (!from_hole && off + nbow > db->arena_cap) {
+        size_t nc = std::max<size_t>(db->arena_cap, 4096); while (nc < off + nbow) nc *= 2;
+        KFCHK(kf_regrow(&db->d_ids, db->arena_end, nc)); KFCHK(kf_regrow(&db->d_vals, db->arena_end, nc));
+        db->arena_cap = nc;
+    }
+    const int slot = db->free_slots.empty() ? db->nslots : db->free_slots.back();
+    const orbhip_status st = kf_ensure_slots(db, slot + 1); if (st != ORBHIP_OK) return st;
+    KfSlot S; S.off = off; S.n = (unsigned)nbow; S.seq = db->next_seq; S.live = 1; S.pad = 0;
+    if (nbow > 0) {
+        KFCHK(hipMemcpyAsync(db->d_ids + off, bow_id, (size_t)nbow * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        KFCHK(hipMemcpyAsync(db->d_vals + off, bow_val, (size_t)nbow * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    KFCHK(hipMemcpyAsync(db->d_slots + slot, &S, sizeof S, hipMemcpyHostToDevice, s));
+    for (int k = 0; k < 2; k++) KFCHK(hipMemsetAsync(db->d_state[k] + slot, 0, sizeof(KfState), s));      // query 0, words 0, score 0.0f
+    KFCHK(hipStreamSynchronize(s));
+    // committed: the host's books follow
+    if (!from_hole) db->arena_end = off + nbow;
+    if (db->free_slots.empty()) { db->nslots++; db->h_slots.push_back(S); } else { db->free_slots.pop_back(); db->h_slots[slot] = S; }
+    db->next_seq++; db->nlive++;
+    *slot_out = slot;
+    return ORBHIP_OK;
+}
+
+static bool kf_live(const orbhip_kfdb* db, int slot) { return slot >= 0 && slot < db->nslots && db->h_slots[slot].live; }
+
+extern "C" orbhip_status orbhip_kfdb_erase(orbhip_kfdb* db, int slot)
+{
+    OrbApiTimer api_timer;
+    if (!db) return orbhip_set_error(ORBHIP_ERR_INVALID, "null database");
+    std::lock_guard<std::mutex> lock(db->m);
+    if (!kf_live(db, slot)) return orbhip_set_error(ORBHIP_ERR_INVALID, "slot %d holds no key frame", slot);
+    KFCHK(hipSetDevice(db->device));
+    hipStream_t s = orbhip_thread_stream(db->device);
+    KfSlot S = db->h_slots[slot]; S.live = 0;
+    KFCHK(hipMemcpyAsync(db->d_slots + slot, &S, sizeof S, hipMemcpyHostToDevice, s));
+    KFCHK(hipStreamSynchronize(s));
+    if (S.n) db->holes.push_back(std::make_pair((size_t)S.off, (size_t)S.n));
+    db->h_slots[slot] = S; db->free_slots.push_back(slot); db->nlive--;
+    return ORBHIP_OK;
+}
+
+static void kf_launch_scan(orbhip_kfdb* db, const int* d_list, int n, const uint32_t* d_qid, const double* d_qval, const int* d_qn, int qn, int qcap, hipStream_t s)
+{
+    KfScanParams P; memset(&P, 0, sizeof P);
+    P.ids = db->d_ids; P.vals = db->d_vals; P.slots = db->d_slots; P.list = d_list; P.n = n;
+    P.q_id = d_qid; P.q_val = d_qval; P.q_n_dev = d_qn; P.q_n = qn; P.q_cap = qcap;
+    P.cnt = db->d_cnt; P.first = db->d_first; P.score = db->d_score;
+    hipLaunchKernelGGL(k_kfdb_scan, dim3((n + KS_T / 64 - 1) / (KS_T / 64), 1, 1), dim3(KS_T, 1, 1), (size_t)std::max(qcap, 1) * sizeof(uint32_t), s, P);
+}
+
+// scan + select + download on stream s, the database's lock held; the query's BowVector is on the device already
+static orbhip_status kf_query_core(orbhip_kfdb* db, int kind, unsigned long long qid, const uint32_t* d_qid, const double* d_qval, const int* d_qn, int qn, int qcap,
+                                   const int* excl, int nexcl, float min_score, orbhip_kfdb_hit* hits, int cap, int* nhits, int* nsharing, int* min_common, hipStream_t s)
+{
+    *nhits = 0; if (nsharing) *nsharing = 0; if (min_common) *min_common = 0;
+    if (db->nslots == 0) return ORBHIP_OK;
+    int ne = 0;
+    if (kind == ORBHIP_KFDB_LOOP && nexcl > 0) {
+        std::vector<int> e; e.reserve((size_t)nexcl);
+        for (int i = 0; i < nexcl; i++) if (excl[i] >= 0 && excl[i] < db->nslots) e.push_back(excl[i]);
+        std::sort(e.begin(), e.end()); e.erase(std::unique(e.begin(), e.end()), e.end());
+        ne = (int)e.size();
+        KFCHK(kf_grow(&db->d_list, &db->list_cap, (size_t)ne));
+        if (ne) { KFCHK(hipMemcpyAsync(db->d_list, e.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice, s)); KFCHK(hipStreamSynchronize(s)); }      // (e leaves scope)
+    }
+    kf_launch_scan(db, nullptr, db->nslots, d_qid, d_qval, d_qn, qn, qcap, s);
+    KfSelectParams Q; memset(&Q, 0, sizeof Q);
+    Q.slots = db->d_slots; Q.state = db->d_state[kind]; Q.nslots = db->nslots; Q.cnt = db->d_cnt; Q.first = db->d_first; Q.score = db->d_score;
+    Q.excl = db->d_list; Q.nexcl = ne; Q.kind = kind; Q.qid = qid; Q.min_score = min_score;
+    Q.flag = db->d_flag; Q.keys = db->d_keys; Q.pay = db->d_pay; Q.cap2 = db->slot_cap; Q.hits = db->d_hits; Q.meta = db->d_meta;
+    hipLaunchKernelGGL(k_kfdb_select, dim3(1, 1, 1), dim3(KSEL_T, 1, 1), 0, s, Q);
+    KFCHK(hipGetLastError());
+    int meta[3] = {0, 0, 0};
+    KFCHK(hipMemcpyAsync(meta, db->d_meta, sizeof meta, hipMemcpyDeviceToHost, s));
+    KFCHK(hipStreamSynchronize(s));
+    if (meta[0] < 0 || meta[0] > db->nslots) return orbhip_set_error(ORBHIP_ERR_HIP, "key-frame database: %d hits among %d slots", meta[0], db->nslots);
+    const int ncopy = std::min(meta[0], cap);
+    if (ncopy > 0) { KFCHK(hipMemcpyAsync(hits, db->d_hits, (size_t)ncopy * sizeof(orbhip_kfdb_hit), hipMemcpyDeviceToHost, s)); KFCHK(hipStreamSynchronize(s)); }
+    *nhits = meta[0]; if (nsharing) *nsharing = meta[1]; if (min_common) *min_common = meta[2];
+    if (meta[0] > cap) return orbhip_set_error(ORBHIP_ERR_CAPACITY, "key-frame database: %d hits, room for %d (the key frames' state is that of the completed query)", meta[0], cap);
+    return ORBHIP_OK;
+}
+
+static orbhip_status kf_upload_query(orbhip_kfdb* db, const uint32_t* bow_id, const double* bow_val, int nbow, hipStream_t s)
+{
+    if (nbow > KFDB_MAX_WORDS) return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "a BowVector of %d words (at most %d)", nbow, KFDB_MAX_WORDS);
+    if (!kf_ascending(bow_id, nbow, db->nwords)) return orbhip_set_error(ORBHIP_ERR_INVALID, "BowVector ids must ascend and lie below %d", db->nwords);
+    if (nbow > 0) {
+        KFCHK(hipMemcpyAsync(db->d_qid, bow_id, (size_t)nbow * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        KFCHK(hipMemcpyAsync(db->d_qval, bow_val, (size_t)nbow * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    return ORBHIP_OK;
+}
+
+extern "C" orbhip_status orbhip_kfdb_query(orbhip_kfdb* db, int kind, uint64_t qid, const uint32_t* bow_id, const double* bow_val, int nbow,
+                                           const int32_t* excluded_slots, int nexcluded, float min_score,
+                                           orbhip_kfdb_hit* hits, int cap, int* nhits, int* nsharing, int* min_common)
+{
+    OrbApiTimer api_timer;
+    if (!db || !nhits || nbow < 0 || cap < 0 || nexcluded < 0 || (kind != ORBHIP_KFDB_RELOC && kind != ORBHIP_KFDB_LOOP) || (nbow > 0 && (!bow_id || !bow_val)) ||
+        (cap > 0 && !hits) || (nexcluded > 0 && !excluded_slots))
+        return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lock(db->m);
+    KFCHK(hipSetDevice(db->device));
+    hipStream_t s = orbhip_thread_stream(db->device);
+    const orbhip_status st = kf_upload_query(db, bow_id, bow_val, nbow, s); if (st != ORBHIP_OK) return st;
+    return kf_query_core(db, kind, qid, db->d_qid, db->d_qval, nullptr, nbow, nbow, excluded_slots, nexcluded, min_score, hits, cap, nhits, nsharing, min_common, s);
+}
+
+extern "C" orbhip_status orbhip_kfdb_query_frame(orbhip_kfdb* db, int kind, uint64_t qid, orbhip_ctx* ctx, orbhip_voc* voc, int frame,
+                                                 const int32_t* excluded_slots, int nexcluded, float min_score,
+                                                 orbhip_kfdb_hit* hits, int cap, int* nhits, int* nsharing, int* min_common)
+{
+    OrbApiTimer api_timer;
+    if (!db || !ctx || !voc || !nhits || cap < 0 || nexcluded < 0 || (kind != ORBHIP_KFDB_RELOC && kind != ORBHIP_KFDB_LOOP) || (cap > 0 && !hits) || (nexcluded > 0 && !excluded_slots))
+        return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    const uint32_t* d_id = nullptr; const double* d_val = nullptr; const int* d_n = nullptr; int qcap = 0, device = 0, nwords = 0; hipStream_t s = nullptr;
+    const orbhip_status st = orbhip_bow_resident(ctx, voc, frame, &d_id, &d_val, &d_n, &qcap, &device, &nwords, &s); if (st != ORBHIP_OK) return st;
+    if (device != db->device || nwords != db->nwords) return orbhip_set_error(ORBHIP_ERR_INVALID, "database for %d words on device %d, vocabulary of %d words on device %d", db->nwords, db->device, nwords, device);
+    std::lock_guard<std::mutex> lock(db->m);
+    KFCHK(hipSetDevice(db->device));
+    return kf_query_core(db, kind, qid, d_id, d_val, d_n, 0, std::min(qcap, KFDB_MAX_WORDS), excluded_slots, nexcluded, min_score, hits, cap, nhits, nsharing, min_common, s);     // on the extractor's stream: behind orbhip_compute_bow
+}
+
+extern "C" orbhip_status orbhip_kfdb_state(orbhip_kfdb* db, int kind, int slot, uint64_t* query, int* words, float* score)
+{
+    if (!db || (kind != ORBHIP_KFDB_RELOC && kind != ORBHIP_KFDB_LOOP)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lock(db->m);
+    if (!kf_live(db, slot)) return orbhip_set_error(ORBHIP_ERR_INVALID, "slot %d holds no key frame", slot);
+    KFCHK(hipSetDevice(db->device));
+    hipStream_t s = orbhip_thread_stream(db->device);
+    KfState st;
+    KFCHK(hipMemcpyAsync(&st, db->d_state[kind] + slot, sizeof st, hipMemcpyDeviceToHost, s));
+    KFCHK(hipStreamSynchronize(s));
+    if (query) *query = st.query;
+    if (words) *words = st.words;
+    if (score) *score = st.score;
+    return ORBHIP_OK;
+}
+
+extern "C" orbhip_status orbhip_kfdb_scores(orbhip_kfdb* db, const uint32_t* bow_id, const double* bow_val, int nbow, const int32_t* slots, int n, double* scores)
+{
+    OrbApiTimer api_timer;
+    if (!db || nbow < 0 || n < 0 || (nbow > 0 && (!bow_id || !bow_val)) || (n > 0 && (!slots || !scores))) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lock(db->m);
+    for (int i = 0; i < n; i++) if (!kf_live(db, slots[i])) return orbhip_set_error(ORBHIP_ERR_INVALID, "slot %d holds no key frame", slots[i]);
+    KFCHK(hipSetDevice(db->device));
+    hipStream_t s = orbhip_thread_stream(db->device);
+    const orbhip_status st = kf_upload_query(db, bow_id, bow_val, nbow, s); if (st != ORBHIP_OK) return st;
+    for (int o = 0; o < n; o += db->slot_cap) {                                   // (one launch unless key frames are named more often than the database has slots)
+        const int m = std::min(n - o, db->slot_cap);
+        KFCHK(kf_grow(&db->d_list, &db->list_cap, (size_t)m));
+        KFCHK(hipMemcpyAsync(db->d_list, slots + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, s));
+        kf_launch_scan(db, db->d_list, m, db->d_qid, db->d_qval, nullptr, nbow, nbow, s);
+        KFCHK(hipGetLastError());
+        KFCHK(hipMemcpyAsync(scores + o, db->d_score, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+        KFCHK(hipStreamSynchronize(s));
+    }
+    return ORBHIP_OK;
+}
+
+// The covisibility accumulation (KeyFrameDatabase.cc:144-196 LOOP, :258-308 RELOC): f32 sums in neighbour order over the state the query left.
+extern "C" orbhip_status orbhip_kfdb_select(orbhip_kfdb* db, int kind, uint64_t qid, int min_common, float min_score, const orbhip_kfdb_hit* hits, int nhits,
+                                            const int32_t* neigh_off, const int32_t* neigh_slot, int32_t* out_slots, int cap, int* nout)
+{
+    OrbApiTimer api_timer;
+    if (!db || !nout || nhits < 0 || cap < 0 || (kind != ORBHIP_KFDB_RELOC && kind != ORBHIP_KFDB_LOOP) || (nhits > 0 && (!hits || !neigh_off)) || (cap > 0 && !out_slots))
+        return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    *nout = 0;
+    if (nhits == 0) return ORBHIP_OK;
+    const int nn = neigh_off[nhits];
+    if (neigh_off[0] != 0 || nn < 0 || (nn > 0 && !neigh_slot)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad neighbour lists");
+    for (int i = 0; i < nhits; i++) if (neigh_off[i + 1] < neigh_off[i]) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad neighbour lists");
+    std::vector<KfState> ns((size_t)nn);
+    std::vector<int> list((size_t)nn);
+    int nslots = 0;
+    {
+        std::lock_guard<std::mutex> lock(db->m);
+        nslots = db->nslots;
+        for (int i = 0; i < nhits; i++) if (hits[i].slot < 0 || hits[i].slot >= nslots) return orbhip_set_error(ORBHIP_ERR_INVALID, "hit %d names slot %d", i, hits[i].slot);
+        for (int j = 0; j < nn; j++) list[j] = kf_live(db, neigh_slot[j]) ? neigh_slot[j] : -1;      // a neighbour that is not in the database was never met by a query
+        if (nn > 0) {
+            KFCHK(hipSetDevice(db->device));
+            hipStream_t s = orbhip_thread_stream(db->device);
+            KFCHK(kf_grow(&db->d_list, &db->list_cap, (size_t)nn)); KFCHK(kf_grow(&db->d_gather, &db->gather_cap, (size_t)nn));
+            KFCHK(hipMemcpyAsync(db->d_list, list.data(), (size_t)nn * sizeof(int), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_kfdb_gather, dim3((nn + 255) / 256, 1, 1), dim3(256, 1, 1), 0, s, db->d_state[kind], db->d_list, nn, db->d_gather);
+            KFCHK(hipGetLastError());
+            KFCHK(hipMemcpyAsync(ns.data(), db->d_gather, (size_t)nn * sizeof(KfState), hipMemcpyDeviceToHost, s));
+            KFCHK(hipStreamSynchronize(s));
+        }
+    }
+    std::vector<float> acc((size_t)nhits); std::vector<int> best((size_t)nhits);
+    float best_acc = kind == ORBHIP_KFDB_LOOP ? min_score : 0.0f;
+    for (int i = 0; i < nhits; i++) {
+        float best_score = hits[i].score, a = hits[i].score; int best_slot = hits[i].slot;
+        for (int j = neigh_off[i]; j < neigh_off[i + 1]; j++) {
+            if (list[j] < 0) continue;
+            const KfState& st = ns[j];
+            if (st.query != qid) continue;
+            if (kind == ORBHIP_KFDB_LOOP && !(st.words > min_common)) continue;
+            a += st.score;
+            if (st.score > best_score) { best_slot = list[j]; best_score = st.score; }
+        }
+        acc[i] = a; best[i] = best_slot;
+        if (a > best_acc) best_acc = a;
+    }
+    const float retain = 0.75f * best_acc;
+    std::vector<int> picked; std::vector<char> seen((size_t)nslots, 0);                             // first occurrence wins (spAlreadyAddedKF)
+    for (int i = 0; i < nhits; i++)
+        if (acc[i] > retain && !seen[best[i]]) { seen[best[i]] = 1; picked.push_back(best[i]); }
+    *nout = (int)picked.size();
+    if (*nout > cap) return orbhip_set_error(ORBHIP_ERR_CAPACITY, "key-frame database: %d candidates, room for %d", *nout, cap);
+    for (size_t i = 0; i < picked.size(); i++) out_slots[i] = picked[i];
+    return ORBHIP_OK;
+}

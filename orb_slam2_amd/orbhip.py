@@ -40,6 +40,8 @@ SYMBOLS = [
     "orbhip_reloc_candidates", "orbhip_runtime_info", "orbhip_device_alloc", "orbhip_device_free", "orbhip_device_upload", "orbhip_device_download",
     "orbhip_device_synchronize", "orbhip_submit_to",
     "orbhip_predict_scale_table", "orbhip_project_search_bounds", "orbhip_project_search_frame", "orbhip_project_best_in_window_bounds", "orbhip_project_best_in_window_batch", "orbhip_project_best_in_window_shared", "orbhip_project_best_in_window_held",
+    "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_clear", "orbhip_kfdb_size", "orbhip_kfdb_add", "orbhip_kfdb_erase", "orbhip_kfdb_query", "orbhip_kfdb_query_frame",
+    "orbhip_kfdb_state", "orbhip_kfdb_scores", "orbhip_kfdb_select",
 ]
 
 
@@ -232,6 +234,19 @@ def lib(path=None):
     L.orbhip_pool_db_shard.restype = None
     L.orbhip_pool_db_query.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.orbhip_reloc_candidates.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, ip]
+    u64p = C.POINTER(C.c_uint64)
+    L.orbhip_kfdb_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int]
+    L.orbhip_kfdb_destroy.argtypes = [vp]
+    L.orbhip_kfdb_destroy.restype = None
+    L.orbhip_kfdb_clear.argtypes = [vp]
+    L.orbhip_kfdb_size.argtypes = [vp]
+    L.orbhip_kfdb_add.argtypes = [vp, vp, vp, C.c_int, ip]
+    L.orbhip_kfdb_erase.argtypes = [vp, C.c_int]
+    L.orbhip_kfdb_query.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, ip, ip, ip]
+    L.orbhip_kfdb_query_frame.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, ip, ip, ip]
+    L.orbhip_kfdb_state.argtypes = [vp, C.c_int, C.c_int, u64p, ip, C.POINTER(C.c_float)]
+    L.orbhip_kfdb_scores.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp]
+    L.orbhip_kfdb_select.argtypes = [vp, C.c_int, C.c_uint64, C.c_int, C.c_float, vp, C.c_int, vp, vp, vp, C.c_int, ip]
     _libs[path] = L
     return L
 
@@ -988,6 +1003,97 @@ class ORBVocabulary:
         id1 = np.ascontiguousarray(id1, np.uint32); id2 = np.ascontiguousarray(id2, np.uint32)
         val1 = np.ascontiguousarray(val1, np.float64); val2 = np.ascontiguousarray(val2, np.float64)
         return self.L_.orbhip_voc_score(self.h, _p(id1), _p(val1), len(id1), _p(id2), _p(val2), len(id2))
+
+
+KFDB_RELOC, KFDB_LOOP = 0, 1          # query kinds (include/orbhip.h)
+KFDB_HIT = np.dtype([("slot", np.int32), ("words", np.int32), ("score", np.float32)])      # orbhip_kfdb_hit
+
+
+class KeyFrameDatabase:
+    """Mirror of ORB_SLAM2::KeyFrameDatabase (KeyFrameDatabase.cc) on a device-resident store of BowVectors.  A key frame is a slot: `add` returns it,
+    `erase` frees it.  `query` is the first half of DetectRelocalizationCandidates (kind KFDB_RELOC) / DetectLoopCandidates (KFDB_LOOP): the scored key
+    frames (lScoreAndMatch) in the reference's order; `select` is the covisibility half over the caller's neighbour lists."""
+
+    def __init__(self, nwords, scoring=0, device=0, library=None):
+        self.L_ = lib(library)
+        self.h = C.c_void_p()
+        self.device, self.nwords = device, int(nwords)
+        _check(self.L_.orbhip_kfdb_create(C.byref(self.h), device, self.nwords, scoring), "orbhip_kfdb_create", self.L_)
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L_.orbhip_kfdb_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.L_.orbhip_kfdb_size(self.h)
+
+    @staticmethod
+    def _bow(bow_id, bow_val):
+        return np.ascontiguousarray(bow_id, np.uint32), np.ascontiguousarray(bow_val, np.float64)
+
+    def add(self, bow_id, bow_val):
+        bid, bval = self._bow(bow_id, bow_val)
+        slot = C.c_int(-1)
+        _check(self.L_.orbhip_kfdb_add(self.h, _p(bid), _p(bval), len(bid), C.byref(slot)), "orbhip_kfdb_add", self.L_)
+        return slot.value
+
+    def erase(self, slot):
+        _check(self.L_.orbhip_kfdb_erase(self.h, int(slot)), "orbhip_kfdb_erase", self.L_)
+
+    def clear(self):
+        _check(self.L_.orbhip_kfdb_clear(self.h), "orbhip_kfdb_clear", self.L_)
+
+    def _run(self, what, call, excluded, cap):
+        ex = np.ascontiguousarray(excluded if excluded is not None else [], np.int32)
+        cap = len(self) if cap is None else int(cap)
+        hits = np.zeros(max(cap, 1), KFDB_HIT)
+        n, ns, mc = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(call(_p(ex), len(ex), _p(hits), cap, C.byref(n), C.byref(ns), C.byref(mc)), what, self.L_)
+        return hits[:n.value].copy(), ns.value, mc.value
+
+    def query(self, kind, qid, bow_id, bow_val, excluded=None, min_score=0.0, cap=None):
+        """-> (hits [KFDB_HIT], number of key frames sharing a word, minCommonWords)"""
+        bid, bval = self._bow(bow_id, bow_val)
+        return self._run("orbhip_kfdb_query", lambda ex, nex, hits, cap, n, ns, mc: self.L_.orbhip_kfdb_query(
+            self.h, kind, int(qid), _p(bid), _p(bval), len(bid), ex, nex, min_score, hits, cap, n, ns, mc), excluded, cap)
+
+    def query_frame(self, kind, qid, extractor, voc, frame=0, excluded=None, min_score=0.0, cap=None):
+        """`query` with the BowVector that voc.compute_bow(extractor, ...) left on the device for `frame`."""
+        return self._run("orbhip_kfdb_query_frame", lambda ex, nex, hits, cap, n, ns, mc: self.L_.orbhip_kfdb_query_frame(
+            self.h, kind, int(qid), extractor.h, voc.h, frame, ex, nex, min_score, hits, cap, n, ns, mc), excluded, cap)
+
+    def state(self, kind, slot):
+        """-> (query, words, score): mnRelocQuery / mnRelocWords / mRelocScore (or the mnLoop* fields) of the slot's key frame"""
+        q, w, sc = C.c_uint64(0), C.c_int(0), C.c_float(0)
+        _check(self.L_.orbhip_kfdb_state(self.h, kind, int(slot), C.byref(q), C.byref(w), C.byref(sc)), "orbhip_kfdb_state", self.L_)
+        return q.value, w.value, np.float32(sc.value)
+
+    def scores(self, bow_id, bow_val, slots):
+        bid, bval = self._bow(bow_id, bow_val)
+        slots = np.ascontiguousarray(slots, np.int32)
+        out = np.zeros(max(len(slots), 1), np.float64)
+        _check(self.L_.orbhip_kfdb_scores(self.h, _p(bid), _p(bval), len(bid), _p(slots), len(slots), _p(out)), "orbhip_kfdb_scores", self.L_)
+        return out[:len(slots)].copy()
+
+    def select(self, kind, qid, min_common, hits, neighbours, min_score=0.0):
+        """neighbours[i] = the slots of GetBestCovisibilityKeyFrames(10) of hits[i]'s key frame -> candidate slots"""
+        hits = np.ascontiguousarray(hits, KFDB_HIT)
+        off = np.zeros(len(hits) + 1, np.int32)
+        off[1:] = np.cumsum([len(v) for v in neighbours], dtype=np.int64)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(v, np.int32).reshape(-1) for v in neighbours]) if len(hits) else [], np.int32)
+        cap = 11 * len(hits) + 1
+        out = np.zeros(cap, np.int32)
+        n = C.c_int(0)
+        _check(self.L_.orbhip_kfdb_select(self.h, kind, int(qid), int(min_common), min_score, _p(hits), len(hits), _p(off), _p(flat), _p(out), cap, C.byref(n)),
+               "orbhip_kfdb_select", self.L_)
+        return out[:n.value].copy()
 
 
 def search_by_bow(mode, desc1, angle1, valid1, fv1, desc2, angle2, valid2, fv2, nnratio=0.7, check_ori=True, device=0, library=None):
