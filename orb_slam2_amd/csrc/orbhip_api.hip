@@ -282,7 +282,7 @@ extern "C" void orbhip_destroy(orbhip_ctx* c)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     prof_collect(c);
     for (auto e : c->pool) (void)hipEventDestroy(e);
-    void* ptrs[] = {c->d_blur_band, c->d_ic_mask, c->d_xgrp, c->d_fc_dma, c->d_geom, c->d_cells, c->d_tiles, c->d_xtab, c->d_ytab, c->d_pattern, c->d_pyr, c->d_blur, c->d_cell_count, c->d_cell_cand,
+    void* ptrs[] = {c->d_blur_band, c->d_ic_mask, c->d_xgrp, c->d_fc_dma, c->d_geom, c->d_cells, c->d_tiles, c->d_runs, c->d_xtab, c->d_ytab, c->d_pattern, c->d_pyr, c->d_blur, c->d_cell_count, c->d_cell_cand,
                     c->d_qt_val, c->d_qt_code, c->d_qt_node, c->d_lvl_kp, c->d_lvl_n[0], c->d_lvl_n[1], c->d_lvl_n[2], c->d_out_block[0], c->d_out_block[1], c->d_out_block[2], c->d_grid_start, c->d_grid_items, c->d_grid_xy, c->d_cand, c->d_top, c->d_ncand,
                     c->d_prev, c->d_m12, c->d_nm};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -425,6 +425,11 @@ extern "C" orbhip_status orbhip_create(orbhip_ctx** out, const orbhip_config* cf
         }
         const int btw = c->blur_mfma ? orbhip_blur_mfma_tile_w() : 128, bth = c->blur_mfma ? orbhip_blur_mfma_tile_h() : 32;     // k_blur_mfma / k_blur workgroup tile
         for (int y0 = 0; y0 < g.h; y0 += bth) for (int x0 = 0; x0 < g.w; x0 += btw) { TileDesc t; t.level = (short)l; t.x0 = (short)x0; t.y0 = (short)y0; t.pad = 0; c->blur_tiles.push_back(t); }
+        if (c->blur_mfma) {   // k_blur_strip's work units: the tiles of a column strip in runs of orbhip_blur_strip_tiles(), top to bottom
+            const int nt = orbhip_blur_strip_tiles(), gy = (g.h + bth - 1) / bth;
+            for (int ty = 0; ty < gy; ty += nt) for (int x0 = 0; x0 < g.w; x0 += btw) { BlurRun r; r.level = (short)l; r.x0 = (short)x0; r.y0 = (short)(ty * bth); r.n = (short)std::min(nt, gy - ty); c->blur_runs.push_back(r); }
+            if (g.w < 8) c->blur_strip_ok = false;      // (its border patch reads the row's last eight columns from the staged tile)
+        }
     }
     c->plane_frame_bytes = (plane_off + 255) & ~255LL; c->cand_slots_per_frame = cand_off; c->qt_per_frame = cand_off;
     c->lvl_kp_per_frame = kp_off; c->out_cap = kp_off; c->lvl0_cap = c->geom[0].kp_cap;
@@ -463,7 +468,7 @@ extern "C" orbhip_status orbhip_create(orbhip_ctx** out, const orbhip_config* cf
     for (int t = 0; t < 256; t++) for (int k = 0; k < 4; k++) pat[(k * 4 + (t >> 6)) * 64 + (t & 63)] = kPatternHost[4 * t + k];
     hipError_t e = hipSuccess;
 #define TRY(x) do { if (e == hipSuccess) e = (x); } while (0)
-    TRY(upload(&c->d_geom, c->geom)); TRY(upload(&c->d_cells, c->cells)); TRY(upload(&c->d_tiles, c->blur_tiles));
+    TRY(upload(&c->d_geom, c->geom)); TRY(upload(&c->d_cells, c->cells)); TRY(upload(&c->d_tiles, c->blur_tiles)); if (!c->blur_runs.empty()) TRY(upload(&c->d_runs, c->blur_runs));
     TRY(upload(&c->d_xtab, c->xtab)); TRY(upload(&c->d_ytab, c->ytab)); TRY(upload(&c->d_xgrp, c->xgrp)); TRY(upload(&c->d_pattern, pat));
     TRY(build_cascade(c));
     if (c->blur_mfma) {   // k_blur_mfma: the two band (Toeplitz) matrices of the 7-tap filter laid out as B operands of v_mfma_i32_32x32x32_i8
@@ -566,6 +571,7 @@ ExtractParams make_params(orbhip_ctx* c, const uint8_t* d_img0, long long frame_
     P.lvl_kp = c->d_lvl_kp; P.lvl_kp_per_frame = c->lvl_kp_per_frame; P.lvl_n = c->d_lvl_n[c->cur];
     P.out_kp = c->d_out_kp[c->cur]; P.out_desc = c->d_out_desc[c->cur]; P.out_n = c->d_out_n[c->cur]; P.out_cap = c->out_cap;
     P.blur_tiles = c->d_tiles; P.nblur_tiles = (int)c->blur_tiles.size(); P.blur_band = c->blur_mfma ? c->d_blur_band : nullptr;
+    if (c->blur_mfma && c->blur_strip_ok) { P.blur_runs = c->d_runs; P.nblur_runs = (int)c->blur_runs.size(); }
     P.xtab = c->d_xtab; P.ytab = c->d_ytab; P.xgrp = c->d_xgrp; P.patternf = c->d_pattern; P.ic_mask = c->d_ic_mask;
     P.pc_xr = c->d_pc_xr; P.pc_yr = c->d_pc_yr; P.pc_ntx = c->pc_ntx; P.pc_nty = c->pc_nty; P.pc_buf0 = c->pc_buf0; P.pc_buf1 = c->pc_buf1; P.pc_xcap = c->pc_xcap; P.pc_ycap = c->pc_ycap;
     P.iniTh = std::min(std::max(c->cfg.ini_th_fast, 0), 255); P.minTh = std::min(std::max(c->cfg.min_th_fast, 0), 255);      // cv::FAST clamps its threshold to [0, 255] (OpenCV 3.2 fast.cpp, FAST_t)

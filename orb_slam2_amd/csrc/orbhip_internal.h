@@ -69,6 +69,8 @@ struct CellDesc {           // one FAST cell (ORBextractor.cc:789-816)
 struct alignas(16) PyrGroup { int sx0; unsigned sel[4]; unsigned coef[4]; int pad[3]; };
 
 struct TileDesc { short level, x0, y0, pad; };
+// k_blur_strip: n vertically adjacent blur tiles (x0, y0), (x0, y0 + tile height), ... of one level: the work of one workgroup per frame
+struct alignas(8) BlurRun { short level, x0, y0, n; };
 
 struct ExtractParams {
     const LevelGeom* geom; int nlevels;
@@ -81,6 +83,7 @@ struct ExtractParams {
     unsigned* lvl_kp; int lvl_kp_per_frame; int* lvl_n;
     orbhip_keypoint* out_kp; uint8_t* out_desc; int* out_n; int out_cap;
     const TileDesc* blur_tiles; int nblur_tiles;
+    const BlurRun* blur_runs; int nblur_runs;                              // the same tiles as runs of one column strip (batches of more than eight frames: k_blur_strip)
     const int4* blur_band;                                                 // k_blur_mfma: band matrices HB1 | HB2 | VB as B operands, [3][64 lanes] x 16 bytes; NULL = k_blur (VALU)
     const int2* xtab; const int2* ytab; const PyrGroup* xgrp;
     const unsigned* ic_mask;                                               // IC_Angle: [32 rows][8 dwords] byte masks of the circular patch (u, v in -15..15, |u| <= umax[|v|])
@@ -174,6 +177,7 @@ void orbhip_launch_pyramid_cascade(const ExtractParams& P, int nframes, hipStrea
 int orbhip_pyramid_tile_dwords();
 int orbhip_blur_mfma_tile_w();
 int orbhip_blur_mfma_tile_h();
+int orbhip_blur_strip_tiles();          // tiles per BlurRun (k_blur_strip)
 bool orbhip_pyramid_tile_fits(int src_cols_per_tile, int src_rows_per_tile);
 void orbhip_launch_to_gray(const uint8_t* src, long long src_frame_stride, int src_row_stride, uint8_t* dst, long long dst_frame_stride,
                            int dst_pitch, int w, int h, int channels, bool rgb_order, int nframes, hipStream_t s);

@@ -3,6 +3,7 @@
 // Kernels (one launch each covers every camera slot of the batch; grid.y / grid.z = frame):
 //   k_pyramid_level  level l from level l-1, fixed-point bilinear        (ORBextractor.cc:1107-1132, cv::resize)
 //   k_blur_mfma      7x7 sigma-2 fixed-point Gaussian as two banded i8 products on the matrix cores, LDS staged (default)
+//   k_blur_strip     the same for batches of more than eight frames: runs of tiles per workgroup, the next tile's rows in flight
 //   k_blur           the same on the VALU (ORBHIP_BLUR=valu)             (ORBextractor.cc:1085-1086, cv::GaussianBlur)
 //   k_fast_cells     ONE WAVEFRONT PER GRID CELL: FAST-9/16 scores in LDS, iniTh/minTh fallback, 3x3 NMS inside
 //                    the cell, row-major emission                          (ORBextractor.cc:789-829, cv::FAST)
@@ -764,24 +765,67 @@ __device__ __forceinline__ void blur_fix(const BlurTile& T, int wave, int lane, 
         }
     }
 }
-__device__ __forceinline__ void blur_compute(const ExtractParams& P, const BlurTile& T, int wave, int lane, const unsigned* s_in, unsigned* s_out, const unsigned* s_band)
+// LDS accesses of k_blur_strip's tile loop, requested without the compiler's knowledge (see lds_read3_issue: as ordinary accesses each would carry
+// `s_waitcnt vmcnt(0)` for the NEXT tile's LDS-DMA in flight).  Other passes: plain accesses.
+struct BlurA { v4i a1; v2i a2; };
+__device__ __forceinline__ BlurA lds_read_blur_a(const unsigned* p1, const unsigned* p2)
 {
-    const LevelGeom& g = T.g; const int x0 = T.t.x0;
-    const int w4 = g.w & ~3;
+    BlurA r;
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    const unsigned a1 = (unsigned)(unsigned long long)(orbhip_lptr)p1, a2 = (unsigned)(unsigned long long)(orbhip_lptr)p2;
+    asm volatile("ds_read_b128 %0, %2\n\tds_read_b64 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r.a1), "=&v"(r.a2) : "v"(a1), "v"(a2));      // (early clobber: the second address is read after the first result is named)
+#else
+    r.a1 = *reinterpret_cast<const v4i*>(p1); r.a2 = *reinterpret_cast<const v2i*>(p2);
+#endif
+    return r;
+}
+__device__ __forceinline__ v4i lds_read_b128(const unsigned* p)
+{
+    v4i r;
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    const unsigned a = (unsigned)(unsigned long long)(orbhip_lptr)p;
+    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r) : "v"(a));
+#else
+    r = *reinterpret_cast<const v4i*>(p);
+#endif
+    return r;
+}
+__device__ __forceinline__ unsigned lds_read_b32_issue(const unsigned* p)
+{
+    unsigned r;
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    const unsigned a = (unsigned)(unsigned long long)(orbhip_lptr)p;
+    asm volatile("ds_read_b32 %0, %1" : "=v"(r) : "v"(a));
+#else
+    r = *p;
+#endif
+    return r;
+}
+__device__ __forceinline__ void lds_write_b32(unsigned* p, unsigned v)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    const unsigned a = (unsigned)(unsigned long long)(orbhip_lptr)p;
+    asm volatile("ds_write_b32 %0, %1" : : "v"(a), "v"(v) : "memory");
+#else
+    *p = v;
+#endif
+}
+// the two banded products and the rounding of a tile's blocks.  kSpelled: the LDS accesses as above (k_blur_strip)
+template <bool kSpelled>
+__device__ __forceinline__ void blur_blocks(int gw, int x0, int he_limit, const v4i& HB1, const v4i& HB2, const v4i& VB, int wave, int lane, const unsigned* s_in, unsigned* s_out)
+{
     const int i = lane & 31, h = lane >> 5;
-    const v4i HB1 = *reinterpret_cast<const v4i*>(s_band + 4 * lane), HB2 = *reinterpret_cast<const v4i*>(s_band + 256 + 4 * lane), VB = *reinterpret_cast<const v4i*>(s_band + 512 + 4 * lane);
     const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // C operand = inline constant 0: the -128 of the operand bytes is undone on the VALU
-    // x86 SSE2 build of OpenCV: cvtps2dq (round-half-even) on whole 4-column groups below w & ~3, the generic rounding behind them
-    const int he_limit = P.blur_round_mode == 1 ? w4 : 0;
     // sum = 2^8 (chi + 128 * 257) + (clo + 128 * 257) with chi / clo the raw products of the (byte - 128) planes: the constant joins the
     // scaling in one fma, exactly (sum < 2^24, K / 2^16 = 129 + 2^-8)
     const float kbias = (float)(257 * 128 * 257) * (1.0f / 65536.0f);
 #pragma unroll 1
     for (int c = wave; c < BM_BLOCKS; c += 4) {
         const int xb = x0 + 32 * c;
-        if (xb >= g.w) break;
-        v4i A1 = *reinterpret_cast<const v4i*>(s_in + i * BM_IN_DW + 8 * c + 4 * h);
-        const v2i a2 = *reinterpret_cast<const v2i*>(s_in + i * BM_IN_DW + 8 * c + 8);
+        if (xb >= gw) break;
+        v4i A1; v2i a2;
+        if (kSpelled) { const BlurA a = lds_read_blur_a(s_in + i * BM_IN_DW + 8 * c + 4 * h, s_in + i * BM_IN_DW + 8 * c + 8); A1 = a.a1; a2 = a.a2; }
+        else { A1 = *reinterpret_cast<const v4i*>(s_in + i * BM_IN_DW + 8 * c + 4 * h); a2 = *reinterpret_cast<const v2i*>(s_in + i * BM_IN_DW + 8 * c + 8); }
         v4i A2 = {a2[0], a2[1], 0, 0};
 #pragma unroll
         for (int d = 0; d < 4; d++) { A1[d] ^= (int)0x80808080u; A2[d] ^= (int)0x80808080u; }
@@ -819,12 +863,18 @@ __device__ __forceinline__ void blur_compute(const ExtractParams& P, const BlurT
                         else v = gx < he_limit ? q : __builtin_floorf(q + 0.5f);
                         out = __builtin_amdgcn_cvt_pk_u8_f32(v, (unsigned)k, out);
                     }
-                    s_out[i * BM_OUT_DW + 8 * c + 2 * gq + h] = out;
+                    if (kSpelled) lds_write_b32(s_out + i * BM_OUT_DW + 8 * c + 2 * gq + h, out); else s_out[i * BM_OUT_DW + 8 * c + 2 * gq + h] = out;
                 }
             };
             if (all_he) finish(std::integral_constant<int, 1>{}); else if (none_he) finish(std::integral_constant<int, 0>{}); else finish(std::integral_constant<int, 2>{});
         }
     }
+}
+__device__ __forceinline__ void blur_compute(const ExtractParams& P, const BlurTile& T, int wave, int lane, const unsigned* s_in, unsigned* s_out, const unsigned* s_band)
+{
+    const v4i HB1 = *reinterpret_cast<const v4i*>(s_band + 4 * lane), HB2 = *reinterpret_cast<const v4i*>(s_band + 256 + 4 * lane), VB = *reinterpret_cast<const v4i*>(s_band + 512 + 4 * lane);
+    // x86 SSE2 build of OpenCV: cvtps2dq (round-half-even) on whole 4-column groups below w & ~3, the generic rounding behind them
+    blur_blocks<false>(T.g.w, T.t.x0, P.blur_round_mode == 1 ? (T.g.w & ~3) : 0, HB1, HB2, VB, wave, lane, s_in, s_out);
 }
 __device__ __forceinline__ void blur_store(const ExtractParams& P, const BlurTile& T, int frame, int wave, int lane, const unsigned* s_out)
 {
@@ -863,6 +913,140 @@ __global__ __launch_bounds__(256, 5) void k_blur_mfma(ExtractParams P)
     blur_mfma_tile(P, tile, frame + P.frame0, s_in, s_out, s_band);
 }
 
+// ---- the batched form (more than eight frames): a workgroup owns a RUN of up to BS_NT vertically adjacent tiles of one column strip and has tile
+// t + 1's rows in flight while it computes tile t - the loop of k_pyramid_level_g (pyr_step), for the same reason: with one tile per workgroup nothing is in
+// flight during the products, a wave waited for 0.51 of its cycles and 301 of its 583 instructions were the scalar prologue (profiles/r06_pmc_summary.json).
+//  * two source buffers; the run's constants (level geometry, source plane, the lane's column offset, border flags, the band matrices in registers) are
+//    read once, through the scalar cache (scalar_load) or by LDS-DMA (band tables): no vector load exists whose wait would be vmcnt(0);
+//  * every LDS access of the loop is spelled out (lds_read_blur_a, lds_write_b32, ...) and its barriers wait for LDS only, so the only vmcnt waits
+//    of the loop body are the counted ones below;
+//  * the border patch reads the staged tile, not memory: the lane whose dword starts at column w & ~3 (and every lane behind it) requests the four bytes
+//    that END at the row's end, columns w-4 .. w-1 - every column a reflected position of the patched dwords refers to lies in the last two whole dwords
+//    or in that one.  (Bytes of the patched dwords that no stored output reads may differ from blur_fix's: positions from w + 4 on.)
+//  * vmcnt: loads and stores of a wave complete in issue order.  Behind tile t's eight row requests the wave issues the stores of tile t - 1 (7 for waves
+//    0 and 1, 6 for waves 2 and 3: a tile that is followed by another has all its 26 rows inside the image) and the eight requests of tile t + 1, so
+//    "all but the newest 8 + stores" is tile t landed, without waiting for those stores.
+#define BS_NT 4                         // tiles per run: k_pyramid_level_g's choice for large batches and the one value measured (profiles/blur_strip_pipeline.txt)
+#define BS_OUT_ROWS 28                  // rows of the output tile in LDS (26 used; every wave reads seven rows w, w + 4, ...)
+__device__ __forceinline__ void blur_strip_issue(const ORBHIP_GLOBAL uint8_t* plane, unsigned spitch, int gh, unsigned coff, int y0, int wave, unsigned* s_in)
+{
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int row = 8 * wave + r;
+        const unsigned roff = (unsigned)reflect101_clamped(y0 - 3 + row, gh) * spitch;      // scalar; a plane is far below 2^31 bytes
+        lds_dma_dword(plane + (roff + coff), reinterpret_cast<uint8_t*>(s_in + row * BM_IN_DW));
+    }
+}
+// the dwords that straddle the image's left / right border, from the staged rows themselves (each wave patches the rows it requested)
+__device__ __forceinline__ void blur_strip_fix(int gw, int x0, bool fix_left, bool fix_right, int wave, int lane, unsigned* s_in)
+{
+    if (!(fix_left || fix_right)) return;                              // wave-uniform
+    const int w4 = gw & ~3;
+    // lane = (row of this wave, slot): slot 0 = the dword left of the image, slots 1 / 2 = the two dwords from column w & ~3 on
+    const int rr = lane >> 3, slot = lane & 7;
+    const int d1 = (w4 - x0 + 4) >> 2;                                 // dword of column w & ~3: holds columns w-4 .. w-1 (1 <= d1 < 64 when fix_right)
+    const bool left = slot == 0 && fix_left, right = (slot == 1 || slot == 2) && fix_right && d1 + slot - 1 < 64;
+    // three staged dwords: A and B = whole dwords from column cA on (the last two in front of column w & ~3; columns 0 .. 7 for the left border), R = columns w-4 .. w-1
+    const int dB = left ? 2 : d1 - 1, dA = max(dB - 1, 0), cA = x0 - 4 + 4 * dA, wlim = left ? 0x7fff : w4;
+    const int cfix = left ? -4 : w4 + 4 * (slot - 1);
+    unsigned* rowp = s_in + (8 * wave + rr) * BM_IN_DW;
+    unsigned A = 0, B = 0, R = 0;
+    if (left || right) {
+        A = lds_read_b32_issue(rowp + dA); B = lds_read_b32_issue(rowp + dB); R = lds_read_b32_issue(rowp + dB + 1);
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(A), "+v"(B), "+v"(R));
+#endif
+    }
+    __builtin_amdgcn_wave_barrier();                                   // slot 1 overwrites the dword that slot 2 has just read
+    if (left || right) {
+        unsigned wv = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int sc = max(reflect101_clamped(cfix + b, gw), cA);
+            const unsigned v = sc >= wlim ? R >> (8 * (sc - (gw - 4))) : ((sc - cA) >> 2 ? B : A) >> (8 * (sc & 3));
+            wv |= (v & 255u) << (8 * b);
+        }
+        lds_write_b32(rowp + (left ? 0 : d1 + slot - 1), wv);
+    }
+}
+struct BlurStrip {
+    const ORBHIP_GLOBAL uint8_t* src; ORBHIP_GLOBAL uint8_t* dst;      // source plane, output plane of this frame
+    unsigned spitch, dpitch, coff; int gw, gh, x0, he_limit; bool fix_left, fix_right;
+};
+// one tile of the run: y0 = its first row, `more` = another tile follows (its rows go to nxt), prev_stores = this wave's stores of the tile before
+__device__ __forceinline__ void blur_strip_step(const BlurStrip& S, int y0, bool more, int prev_stores, const v4i& HB1, const v4i& HB2, const v4i& VB,
+                                                int wave, int lane, unsigned* cur, unsigned* nxt, unsigned* s_out)
+{
+    if (more) {
+        blur_strip_issue(S.src, S.spitch, S.gh, S.coff, y0 + BM_ROWS, wave, nxt);
+        if (prev_stores == 0) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(8));
+        else if (prev_stores == 7) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(15));
+        else __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(14));
+    } else {
+        if (prev_stores == 0) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(0));
+        else if (prev_stores == 7) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(7));
+        else __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(6));
+    }
+    __builtin_amdgcn_wave_barrier();                                   // every lane's dwords have landed before any lane patches one
+    blur_strip_fix(S.gw, S.x0, S.fix_left, S.fix_right, wave, lane, cur);
+    lds_barrier_spelled();
+    blur_blocks<true>(S.gw, S.x0, S.he_limit, HB1, HB2, VB, wave, lane, cur, s_out);
+    lds_barrier_spelled();
+    // store: wave w writes output rows w, w + 4, ..., lane = dword of the row (224 contiguous bytes per instruction)
+    const unsigned* op = s_out + wave * BM_OUT_DW + min(lane, 8 * BM_BLOCKS - 1);
+    unsigned v[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++) v[k] = lds_read_b32_issue(op + 4 * k * BM_OUT_DW);
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]));
+#endif
+    const int gx = S.x0 + 4 * lane;
+    if (lane < 8 * BM_BLOCKS && gx < S.gw) {
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            const int r = wave + 4 * k;
+            if (r < BM_ROWS && y0 + r < S.gh) *reinterpret_cast<ORBHIP_GLOBAL unsigned*>(S.dst + ((unsigned)(y0 + r) * S.dpitch + (unsigned)gx)) = v[k];   // pitch multiple of 64, gx of 4: pad bytes absorb the tail
+        }
+    }
+}
+__global__ __launch_bounds__(256, 5) void k_blur_strip(ExtractParams P)
+{
+    __shared__ __attribute__((aligned(16))) unsigned s_in0[32 * BM_IN_DW], s_in1[32 * BM_IN_DW], s_band[3 * 64 * 4];
+    __shared__ unsigned s_out[BS_OUT_ROWS * BM_OUT_DW];
+    int run, frame;
+    if (!xcd_frame_map(P.nblur_runs, P.nframes, run, frame)) return;
+    frame += P.frame0;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    // the band matrices HB1 | HB2 | VB: twelve 256-byte rows, three per wave
+    const ORBHIP_GLOBAL uint8_t* band = uniform_ptr(reinterpret_cast<const uint8_t*>(P.blur_band));
+#pragma unroll
+    for (int k = 0; k < 3; k++) lds_dma_dword(band + (unsigned)(256 * (3 * wave + k) + 4 * lane), reinterpret_cast<uint8_t*>(s_band + 64 * (3 * wave + k)));
+    const unsigned long long rw = scalar_load(reinterpret_cast<const unsigned long long*>(P.blur_runs + run));      // (one s_load_dwordx2)
+    BlurRun R; R.level = (short)rw; R.x0 = (short)(rw >> 16); R.y0 = (short)(rw >> 32); R.n = (short)(rw >> 48);
+    const LevelGeom* gp = P.geom + R.level;
+    BlurStrip S;
+    S.gw = scalar_load(&gp->w); S.gh = scalar_load(&gp->h); S.x0 = R.x0;
+    const int gpitch = scalar_load(&gp->pitch), plane_off = scalar_load(&gp->plane_off);
+    S.spitch = (unsigned)(R.level == 0 ? P.img0_pitch : gpitch); S.dpitch = (unsigned)gpitch;
+    S.src = uniform_ptr(R.level == 0 ? P.img0 + (long long)frame * P.img0_frame_stride : P.pyr + (long long)frame * P.plane_frame_bytes + plane_off);
+    S.dst = uniform_ptr(P.blur + (long long)frame * P.plane_frame_bytes + plane_off);
+    const int w4 = S.gw & ~3;
+    S.coff = (unsigned)min(max(S.x0 - 4 + 4 * lane, 0), S.gw - 4);      // dwords that are not entirely inside the image: see blur_strip_fix
+    S.fix_left = S.x0 == 0; S.fix_right = S.x0 + 252 > w4;
+    S.he_limit = P.blur_round_mode == 1 ? w4 : 0;                       // x86 SSE2 build of OpenCV: cvtps2dq (round-half-even) on whole 4-column groups below w & ~3
+    blur_strip_issue(S.src, S.spitch, S.gh, S.coff, R.y0, wave, s_in0);
+    __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(8));                        // the band rows
+    lds_barrier_spelled();
+    const v4i HB1 = lds_read_b128(s_band + 4 * lane), HB2 = lds_read_b128(s_band + 256 + 4 * lane), VB = lds_read_b128(s_band + 512 + 4 * lane);
+    const int n = R.n, full = wave < 2 ? 7 : 6;
+    for (int t = 0; t < n; t += 2) {                                   // (two steps per trip: the buffers swap roles with constant addresses)
+        blur_strip_step(S, R.y0 + BM_ROWS * t, t + 1 < n, t ? full : 0, HB1, HB2, VB, wave, lane, s_in0, s_in1, s_out);
+        if (t + 1 < n) blur_strip_step(S, R.y0 + BM_ROWS * (t + 1), t + 2 < n, full, HB1, HB2, VB, wave, lane, s_in1, s_in0, s_out);
+    }
+}
+int orbhip_blur_strip_tiles() { return BS_NT; }
+
+
 void orbhip_launch_blur(const ExtractParams& P, const int gk[4], int nframes, hipStream_t s, int tile0, int ntiles)
 {   // tiles [tile0, tile0 + ntiles) of the level-major tile list (ntiles < 0: all)
     BlurK K; K.k0 = (float)gk[0]; K.k1 = (float)gk[1]; K.k2 = (float)gk[2]; K.k3 = (float)gk[3];
@@ -871,7 +1055,8 @@ void orbhip_launch_blur(const ExtractParams& P, const int gk[4], int nframes, hi
     ExtractParams Q = P; Q.nframes = nframes;
     if (ntiles >= 0) { Q.blur_tiles = P.blur_tiles + tile0; Q.nblur_tiles = ntiles; }
     if (Q.nblur_tiles <= 0) return;
-    if (P.blur_band) hipLaunchKernelGGL(k_blur_mfma, dim3(xcd_grid(Q.nblur_tiles, nframes), 1, 1), dim3(256, 1, 1), 0, s, Q);
+    if (P.blur_band && nframes > 8 && ntiles < 0 && P.blur_runs) hipLaunchKernelGGL(k_blur_strip, dim3(xcd_grid(P.nblur_runs, nframes), 1, 1), dim3(256, 1, 1), 0, s, Q);
+    else if (P.blur_band) hipLaunchKernelGGL(k_blur_mfma, dim3(xcd_grid(Q.nblur_tiles, nframes), 1, 1), dim3(256, 1, 1), 0, s, Q);
     else hipLaunchKernelGGL(k_blur, dim3(xcd_grid(Q.nblur_tiles, nframes), 1, 1), dim3(256, 1, 1), 0, s, Q, K);
 }
 
