@@ -6,6 +6,7 @@ that takes the batched path - through extract_batch: the border shapes of the 22
 that ends exactly at the border; top levels with fewer tile rows than a run holds, level 0 with 9-10 tile rows), both GaussianBlur rounding
 modes, the serial schedule, and a height of 13 tile rows, which leaves a single tile in the last run of every level-0 strip for runs of 2, 3
 and 4 tiles alike (the step that has no tile to prefetch then follows one that prefetched).
+Everything above eleven frames - every slot of a batch, frame offsets, the larger run lengths of the pyramid - is in tests/test_large_batches.py.
 
 backend = "emu" (kernel sources under the test-only fiber emulation, CPU) or "gpu" (real liborbhip.so, marked gpu).
 """

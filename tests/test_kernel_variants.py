@@ -52,7 +52,8 @@ def test_blur_kernels_and_rounding_modes(backend, oracle, env, blur, mode, w, h)
 
 @pytest.mark.parametrize("serial", [0, 1])
 def test_second_stream_and_serial_schedule(backend, oracle, env, serial):
-    """a batch of more than eight frames puts the blur on the context's second stream beside the quadtree; ORBHIP_SERIAL=1 keeps every kernel on one"""
+    """a batch of more than eight frames puts the blur on the context's second stream beside the quadtree; ORBHIP_SERIAL=1 keeps every kernel on one
+    (eleven frames, four of them compared; everything above eleven frames and every slot: tests/test_large_batches.py)"""
     env(ORBHIP_SERIAL=serial)
     w, h, n, B = 320, 240, 300, 11
     imgs = np.stack([synth.frame(w, h, seed=40 + s) for s in range(B)])
