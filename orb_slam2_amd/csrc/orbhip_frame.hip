@@ -3,6 +3,7 @@
 #include "orbhip_ctx.h"
 
 // ---------------------------------------------------------------------------------------------- stereo
+// k_stereo_rows drops items beyond this bound (`if (p < T.row_cap)`); none exists: a key point enters ceil(y+r) - floor(y-r) + 1 < 2r + 3 <= ceil(4*sf[L-1]) + 3 rows, a frame has at most out_cap
 int stereo_row_cap(const orbhip_ctx* c) { return c->out_cap * ((int)ceilf(4.0f * c->sf[c->L - 1]) + 3); }      // rows [floor(y-r), ceil(y+r)], r = 2*scale
 StereoSide stereo_side(orbhip_ctx* c)
 {

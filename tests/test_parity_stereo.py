@@ -1,5 +1,7 @@
 """Frame::ComputeStereoMatches (Frame.cc:466-640) on the device-resident results of a left and a right
-extractor: mvuRight / mvDepth bit-identical to the oracle's restatement."""
+extractor: mvuRight / mvDepth bit-identical to the oracle's restatement.
+The shapes here stay below 2000 key points and 520 rows, with uniform disparity and a disparity limit far beyond it; the matcher's limits (more than
+4096 key points, 1040 rows and more, a limit that binds, varying disparity, a handful of matches) are in tests/test_stereo_limits.py."""
 import numpy as np
 import pytest
 

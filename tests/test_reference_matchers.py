@@ -74,16 +74,26 @@ def test_search_for_initialization(ref, oracle, pair, window, ratio, ori):
     assert n_o > 40
 
 
-@pytest.mark.parametrize("w,h,n,seed,disp", [(480, 360, 700, 5, 12), (640, 480, 1000, 6, 25), (1241, 376, 2000, 7, 40), (400, 300, 500, 8, 3), (640, 480, 800, 9, 60)])
-def test_compute_stereo_matches(ref, oracle, w, h, n, seed, disp):
+# the last three: the regimes of tests/test_stereo_limits.py - more than 4096 key points and accepted matches, more than 1024 rows, and a disparity
+# limit (maxD = fx in the reference) one pixel beyond the scene's 21 px
+STEREO_CASES = [(480, 360, 700, 5, 12, FX), (640, 480, 1000, 6, 25, FX), (1241, 376, 2000, 7, 40, FX), (400, 300, 500, 8, 3, FX), (640, 480, 800, 9, 60, FX),
+                (752, 480, 6000, 11, 12, FX), (640, 1040, 1500, 12, 10, FX), (480, 360, 600, 5, 21, np.float32(22.0))]
+
+
+@pytest.mark.parametrize("w,h,n,seed,disp,fx", [pytest.param(*c, id="-".join(str(v) for v in c[:5]) + ("" if c[5] == FX else "-fx%g" % c[5])) for c in STEREO_CASES])
+def test_compute_stereo_matches(ref, oracle, w, h, n, seed, disp, fx):
     """Frame::Frame (stereo): two extractor threads + ComputeStereoMatches.  The reference reads `mb` before it assigns it
     (Frame.cc:89 vs :113); the wrapper pre-seeds the member with mbf / fx."""
     L, R = stereo_pair(w, h, seed, disp)
-    F = ref.RefFrame(L, R, nfeatures=n, fx=float(FX), fy=float(FX), cx=607.1928, cy=185.2157, bf=float(BF))
+    F = ref.RefFrame(L, R, nfeatures=n, fx=float(fx), fy=float(fx), cx=607.1928, cy=185.2157, bf=float(BF))
     eL, eR = oracle.OracleExtractor(n, 1.2, 8, 20, 7), oracle.OracleExtractor(n, 1.2, 8, 20, 7)
     kl, _ = eL.extract(L)
     eR.extract(R)
-    uo, do = oracle.stereo_matches(eL, eR, BF, BF / FX)
+    uo, do = oracle.stereo_matches(eL, eR, BF, BF / fx)
+    if n == 6000:
+        assert len(kl) > 4096 and int((uo >= 0).sum()) > 4096
+    if fx < 100:
+        assert 0 < int((uo >= 0).sum()) < int((oracle.stereo_matches(eL, eR, BF, BF / FX)[0] >= 0).sum()) - 20       # the limit binds
     assert F.keys.tobytes() == kl.tobytes()
     assert F.u_right.tobytes() == uo.tobytes() and F.depth.tobytes() == do.tobytes()
     assert int((uo >= 0).sum()) > n // 4
