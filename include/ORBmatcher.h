@@ -89,6 +89,9 @@ public:
     // direction, scale-invariance range, mfMaxDistance and descriptor read in place under the point's own mutexes.  Defined in ORBmatcher.cc; declared here
     // because friendship reaches the class's members (this nested type is one), not the file's free functions.  No data member: the class layout is the reference's.
     struct Access;
+    // ... and the ones of ComputeDistinctiveDescriptorsBatch (include/ORBmatcherBatch.h): mObservations read, mDescriptor written, both under mMutexFeatures as
+    // MapPoint::ComputeDistinctiveDescriptors does.  Defined in MapPointBatch.cc.
+    struct DistinctAccess;
 
 protected:
     // helpers of the reference's own bodies (ORBmatcher.cc:131-157, 1601-1642); the GPU entry points carry their own versions

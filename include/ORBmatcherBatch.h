@@ -8,6 +8,8 @@
 // (orbhip_search_by_bow_batch, orbhip_search_for_triangulation_batch, orbhip_search_best_in_window_batch of include/orbhip.h) and return, per key frame,
 // exactly what the member returns when it is called in the reference's order.  They are defined in orb_slam2_amd/cpp/ORBmatcher.cc (the file
 // integration/apply_dropin.py installs as src/ORBmatcher.cc); INTEGRATION.md section 2-3h shows the three loops rewritten.  Failures throw ORBhipError like the members'.
+// A fourth loop belongs to MapPoint: pMP->ComputeDistinctiveDescriptors() for every map point of a key frame (LocalMapping.cc:140-161, 517-530).  Its batch
+// form is defined in orb_slam2_amd/cpp/MapPointBatch.cc (installed as src/MapPointBatch.cc); INTEGRATION.md section 2-3k.
 #ifndef ORBMATCHERBATCH_H
 #define ORBMATCHERBATCH_H
 
@@ -37,6 +39,11 @@ int TriangulationPairs(KeyFrame* pKF1, const std::vector<int> &vMatches12, std::
 // The points travel once for all targets (orbhip_project_best_in_window_shared) and a re-check searches the target's slot where that call left it on the
 // device (orbhip_project_best_in_window_held); more than 64 targets, or a cv::Mat whose R*x+t rounding the probe does not know (H11 mode 2): one copy per target.
 int FuseBatch(const std::vector<KeyFrame*> &vpTargetKFs, const std::vector<MapPoint*> &vpMapPoints, const float th = 3.0);
+
+// = pMP->ComputeDistinctiveDescriptors() for every element in order (NULL elements skipped); one device call for all of them
+// (orbhip_distinctive_descriptors).  The points are independent of one another, so the batch is exact; equal medians break as the member breaks them in
+// this process (the order of std::map<KeyFrame*,size_t>).
+void ComputeDistinctiveDescriptorsBatch(const std::vector<MapPoint*> &vpMapPoints);
 
 } // namespace ORB_SLAM2
 

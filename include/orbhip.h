@@ -229,6 +229,15 @@ orbhip_status orbhip_nn_expand_device(void* stream, const uint8_t* d_db, int64_t
 orbhip_status orbhip_hamming_nn_device_expanded(void* stream, const uint8_t* d_q, int nq, const uint8_t* d_db, const uint8_t* d_expanded, int64_t ndb,
                                                 int64_t db_index_base, int64_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist);
 
+/* MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:242-307) for npoints map points in one call.  Group g = descriptors offsets[g] .. offsets[g+1]-1 of
+   desc (the point's observations in the caller's order, N of them).  Row i of the group holds the N distances d(i, j), d(i, i) = 0 included; its median is
+   its k-th smallest value, k = (N-1)/2 rounded down (= vDists[0.5*(N-1)] of the sorted row); best_index[g] is the FIRST row with the strictly smallest median
+   and best_median[g] that median (N = 1 and N = 2: index 0, median 0).  An empty group gives -1 and -1.  The reference breaks equal medians by the order of
+   its std::map<KeyFrame*,size_t>, this entry by position in the caller's array.  Re-entrant like every matcher entry on host arrays: one
+   upload, one launch set and one download of 8 bytes per group on the calling thread's own stream.  npoints == 0 touches nothing. */
+orbhip_status orbhip_distinctive_descriptors(int device, const uint8_t* desc /* total x 32 */, const int32_t* offsets /* npoints + 1, non-decreasing, offsets[0] = 0 */,
+                                             int npoints, int32_t* best_index /* npoints */, int32_t* best_median /* npoints, may be NULL */);
+
 /* ORBmatcher(nnratio, check_ori).SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, window)
    (ORBmatcher.h:69, ORBmatcher.cc:405-520) on host buffers.  The Frame members it reads are passed flat:
    mvKeysUn / mDescriptors of both frames and the image bounds (mnMinX = mnMinY = 0, mnMaxX = im_w,

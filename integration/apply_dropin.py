@@ -16,6 +16,7 @@ What it produces (nothing else of the checkout changes; Tracking.cc, LocalMappin
     out/include/ORBextractor.h, out/src/ORBextractor.cc     the drop-in extractor class (include/ORBextractor.h, orb_slam2_amd/cpp/ORBextractor.cc)
     out/include/ORBmatcher.h,   out/src/ORBmatcher.cc       the drop-in matcher class: all twelve members (orb_slam2_amd/cpp/ORBmatcher.cc)
     out/include/ORBmatcherBatch.h                           the back end's matcher loops as single device passes (optional use)
+    out/src/MapPointBatch.cc                                ComputeDistinctiveDescriptorsBatch of that header: a NEW file, to be added to the library's sources in CMakeLists.txt
     out/include/orbhip_gemm_probe.h                         how the linked cv::Mat rounds `R*x+t` (ORBmatcher.cc asks once per process, DESIGN.md H11)
     out/include/orbhip.h                                    the C ABI of liborbhip.so (link with -lorbhip)
   EDITED (located by the reference's own statements; the script fails loudly - never skips silently - where a checkout differs from upstream):
@@ -199,7 +200,7 @@ def main():
               "include/MapPoint.h": patch_mappoint_header(open(os.path.join(ref, "include/MapPoint.h")).read())}
     copies = {"include/ORBextractor.h": "include/ORBextractor.h", "src/ORBextractor.cc": "orb_slam2_amd/cpp/ORBextractor.cc", "include/orbhip.h": "include/orbhip.h",
               "include/ORBmatcher.h": "include/ORBmatcher.h", "src/ORBmatcher.cc": "orb_slam2_amd/cpp/ORBmatcher.cc", "include/ORBmatcherBatch.h": "include/ORBmatcherBatch.h",
-              "include/orbhip_gemm_probe.h": "include/orbhip_gemm_probe.h"}
+              "src/MapPointBatch.cc": "orb_slam2_amd/cpp/MapPointBatch.cc", "include/orbhip_gemm_probe.h": "include/orbhip_gemm_probe.h"}
     if kfdb:
         copies.update({"include/KeyFrameDatabase.h": "include/KeyFrameDatabase.h", "src/KeyFrameDatabase.cc": "orb_slam2_amd/cpp/KeyFrameDatabase.cc"})
     if emit_patch:

@@ -1,5 +1,5 @@
 // orbhip_ctx.h — the extractor context and what the host translation units share (orbhip_api.hip, orbhip_host_path.hip, orbhip_search.hip,
-// orbhip_frame.hip).  Host code only: no kernel file includes it.
+// orbhip_frame.hip, the host half of orbhip_distinct.hip).  Host code only: no kernel reads it.
 #pragma once
 #include "orbhip_internal.h"
 #include <cmath>
@@ -104,6 +104,18 @@ struct ProfScope {       // counts = 0: a further part of a kernel that is launc
 // ---------------------------------------------------------------------------------------------- small helpers
 template <typename T> static hipError_t dalloc(T** p, size_t count) { return orbhip_dmalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)); }
 static bool device_present() { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n >= 1; }
+
+// One matcher call on the calling thread's arena: lay it out (above floor, see arena_layout), upload its inputs, launch, download its answers.
+// After a failure the stream is synchronised: never leave a copy in flight on the per-thread mirrors.
+template <typename Layout, typename Launch> static hipError_t arena_call(int device, hipStream_t s, Layout layout, Launch launch, size_t floor = 0)
+{
+    hipError_t e = arena_layout(device, layout, floor);
+    if (e == hipSuccess) e = arena_upload(s);
+    if (e == hipSuccess) { launch(); e = hipGetLastError(); }
+    if (e == hipSuccess) e = arena_download(s);
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);
+    return e;
+}
 
 // ---------------------------------------------------------------------------------------------- functions that one host file defines and another calls
 // (hidden: they are not part of the library's dynamic symbol table)

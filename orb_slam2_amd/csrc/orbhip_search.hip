@@ -2,18 +2,6 @@
 // shared / held), the stateless matcher entry points and the relocalisation candidates.  Kernels: orbhip_kernels_proj.hip, orbhip_kernels_match.hip.
 #include "orbhip_ctx.h"
 
-// One matcher call on the calling thread's arena: lay it out (above floor, see arena_layout), upload its inputs, launch, download its answers.
-// After a failure the stream is synchronised: never leave a copy in flight on the per-thread mirrors.
-template <typename Layout, typename Launch> static hipError_t arena_call(int device, hipStream_t s, Layout layout, Launch launch, size_t floor = 0)
-{
-    hipError_t e = arena_layout(device, layout, floor);
-    if (e == hipSuccess) e = arena_upload(s);
-    if (e == hipSuccess) { launch(); e = hipGetLastError(); }
-    if (e == hipSuccess) e = arena_download(s);
-    if (e != hipSuccess) (void)hipStreamSynchronize(s);
-    return e;
-}
-
 // the slots orbhip_project_best_in_window_shared left in the calling thread's scratch (valid while orbhip_tl_held_valid, orbhip_api.hip)
 static thread_local struct HeldSlots { int device = -1; size_t floor = 0; std::vector<BestParams> B; std::vector<int> live_of_slot; } g_held;
 

@@ -20,7 +20,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
 
 # every symbol include/orbhip.h declares (tests check the library exports all of them)
 SYMBOLS = [
-    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
+    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
     "orbhip_get_scale_tables", "orbhip_level_size", "orbhip_extract", "orbhip_extract_batch", "orbhip_pyramid_level",
     "orbhip_extract_device", "orbhip_sync", "orbhip_fetch", "orbhip_fetch_matches", "orbhip_descriptor_distance",
     "orbhip_hamming_nn", "orbhip_hamming_nn_device", "orbhip_nn_expanded_size", "orbhip_nn_expand_device", "orbhip_hamming_nn_device_expanded", "orbhip_search_for_initialization", "orbhip_profile_enable",
@@ -183,6 +183,7 @@ def lib(path=None):
     L.orbhip_fetch_matches.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
     L.orbhip_descriptor_distance.argtypes = [vp, vp]
     L.orbhip_hamming_nn.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.orbhip_distinctive_descriptors.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp]
     L.orbhip_hamming_nn_device.argtypes = [vp, vp, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.orbhip_nn_expanded_size.argtypes = [C.c_int64]; L.orbhip_nn_expanded_size.restype = C.c_size_t
     L.orbhip_nn_expand_device.argtypes = [vp, vp, C.c_int64, vp]
@@ -900,6 +901,22 @@ def hamming_nn(q, db, device=0, index_base=0, library=None):
     L = lib(library)
     _check(L.orbhip_hamming_nn(device, _p(q), len(q), _p(db), len(db), index_base, _p(bi), _p(bd), _p(sd)), "orbhip_hamming_nn", L)
     return bi, bd, sd
+
+
+def distinctive_descriptors(desc, offsets, device=None, library=None):
+    """MapPoint::ComputeDistinctiveDescriptors for len(offsets) - 1 map points in one device call: group g is desc[offsets[g]:offsets[g + 1]], the point's
+    observations.  Returns (best_index, best_median) per group, int32: the first row with the strictly smallest median of its distances to the whole group,
+    and that median; -1 and -1 for an empty group."""
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    offsets = np.ascontiguousarray(offsets, np.int32)
+    if offsets.ndim != 1 or len(offsets) < 1 or (len(offsets) > 1 and int(offsets[-1]) > len(desc)):
+        raise ValueError("offsets: npoints + 1 values, the last one at most len(desc)")
+    n = len(offsets) - 1
+    bi = np.zeros(n, np.int32)
+    bm = np.zeros(n, np.int32)
+    L = lib(library)
+    _check(L.orbhip_distinctive_descriptors(0 if device is None else device, _p(desc), _p(offsets), n, _p(bi), _p(bm)), "orbhip_distinctive_descriptors", L)
+    return bi, bm
 
 
 def nn_expanded_size(ndb, library=None):
