@@ -339,7 +339,8 @@ orbhip_status orbhip_search_best_in_window(int device, const orbhip_keypoint* kp
    FeatureVector (std::map in the reference) are returned flattened in map (ascending key) order:
      bow_id[i], bow_val[i]                      i < nbow           BowVector: word id -> weight (double)
      fv_node[j], fv_feat[fv_off[j] .. fv_off[j+1])  j < nfv        FeatureVector: node id -> feature indices, ascending
-   Caller buffers hold n entries (fv_off: n + 1).  At most 7168 features per frame. */
+   Caller buffers hold n entries (fv_off: n + 1).  At most 8192 features per frame: more is ORBHIP_ERR_UNSUPPORTED, nothing is
+   computed and the vocabulary stays usable. */
 typedef struct orbhip_voc orbhip_voc;
 /* TemplatedVocabulary::loadFromTextFile (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1425; System.cc:68).  Blank lines
    are ignored (the reference reads uninitialised variables on the empty last line of a newline-terminated file). */
@@ -365,7 +366,9 @@ orbhip_status orbhip_fetch_bow(orbhip_ctx* ctx, orbhip_voc* voc, int frame, uint
    mvKeysUn[i].angle; side 2 the frame (mode 0: mvKeys[i].angle, valid2 ignored) or the second key frame (mode 1: valid2
    likewise).  fvX_* = the FeatureVector flattened as returned by orbhip_voc_transform.  match12[i1] = index on side 2 or -1;
    the caller writes vpMapPointMatches[match12[i1]] = vpMapPoints1[i1] (mode 0) / vpMatches12[i1] = vpMapPoints2[match12[i1]]
-   (mode 1).  *nmatches = the reference's return value.  Synchronous, host pointers. */
+   (mode 1).  *nmatches = the reference's return value.  Synchronous, host pointers.
+   A vocabulary node may hold at most 8192 features of side 2.  With a larger one the call returns ORBHIP_ERR_UNSUPPORTED, every
+   match12[i] is -1 and *nmatches is 0; the next call on the thread is unaffected.  (orbhip_search_for_triangulation has no such limit.) */
 orbhip_status orbhip_search_by_bow(int device, int mode,
                                    const uint8_t* desc1, const float* angle1, const uint8_t* valid1, int n1,
                                    const uint32_t* fv1_node, const int32_t* fv1_off, const uint32_t* fv1_feat, int nfv1,
@@ -399,7 +402,9 @@ typedef struct {
 } orbhip_bow_side;
 typedef struct { const orbhip_bow_side* side1; const orbhip_bow_side* side2; int32_t* match12 /* side1->n entries */; int32_t nmatches; } orbhip_bow_pair;
 /* npairs independent SearchByBoW calls (mode as in orbhip_search_by_bow).  Sides are recognised by POINTER: a side that several pairs name
-   (the current frame of Relocalization, the current key frame of LoopClosing::ComputeSim3) is uploaded once. */
+   (the current frame of Relocalization, the current key frame of LoopClosing::ComputeSim3) is uploaded once.
+   The batch succeeds or fails as a whole: if ANY pair has a node with more than 8192 features of side 2, the call returns
+   ORBHIP_ERR_UNSUPPORTED and EVERY pair's match12 is all -1 and its nmatches 0, the pairs without such a node included. */
 orbhip_status orbhip_search_by_bow_batch(int device, int mode, int npairs, orbhip_bow_pair* pairs, float nnratio, int check_ori);
 
 typedef struct {

@@ -221,6 +221,65 @@ def test_search_for_triangulation(ref, oracle, pair_oracle, fx, cx, cy, stereo, 
     F1.close(); F2.close()
 
 
+def _forced_partitions(n1, n2, rng, partner):
+    """FeatureVectors over the features of a natural frame pair with the partition into nodes chosen freely (feature indices ascending inside a node, as
+    FeatureVector::addFeature leaves them): the shapes tests/test_bow_node_shapes.py builds.  Side 2 is cut at random into nodes of the wanted sizes; a side-1
+    feature goes to the node of its partner (partner[i]: its match with everything in one node, or -1: a node at random), so the nodes keep true pairs.
+    -> {name: (fv1, fv2)}"""
+    def flat(ids, node_of):
+        """the FeatureVector that puts feature i into node ids[node_of[i]] (-1: nowhere)"""
+        present = [k for k in range(len(ids)) if np.any(node_of == k)]
+        feats = [np.nonzero(node_of == k)[0] for k in present]
+        return np.array([ids[k] for k in present], np.uint32), np.concatenate([[0], np.cumsum([len(f) for f in feats])]).astype(np.int32), np.concatenate(feats).astype(np.uint32)
+
+    def pair(ids, cuts2, drop1=(), drop2=()):
+        node2 = np.empty(n2, np.int64)
+        node2[rng.permutation(n2)] = np.repeat(np.arange(len(ids)), np.diff(cuts2))
+        node1 = np.where(partner >= 0, node2[np.maximum(partner, 0)], rng.integers(0, len(ids), n1))
+        node1[np.isin(node1, drop1)] = -1; node2[np.isin(node2, drop2)] = -1
+        return flat(ids, node1), flat(ids, node2)
+    return {"one_node": pair([5], [0, n2]),
+            "edges": pair([3, 4, 9, 17, 40], [0, 64, 129, 385, 642, n2]),                     # side 2 cut at exactly 64 / 65 / 256 / 257, the rest in the last node
+            "small_nodes": pair(list(range(10, 610, 2)), np.linspace(0, n2, 301).astype(int)),      # 300 nodes of 2 - 3 side-2 features
+            "one_sided": pair(list(range(20)), np.linspace(0, n2, 21).astype(int), drop1=[1, 4, 7, 10, 13], drop2=[2, 5, 8, 11, 14])}
+
+
+@pytest.mark.parametrize("shape", ["one_node", "edges", "small_nodes", "one_sided"])
+def test_matchers_at_forced_node_shapes(ref, oracle, pair, shape):
+    """The oracle's merge-join and in-node order against the reference's SearchByBoW (both overloads) and SearchForTriangulation where the partition of a
+    natural frame pair's features into nodes is forced: everything in one node, side-2 nodes of exactly 64 / 65 / 256 / 257 features, 300 nodes of two or
+    three, nodes that only one side has."""
+    w, h, n, seq, sf, K, F = pair
+    (k1, d1), (k2, d2) = K
+    rng = np.random.default_rng(len(shape))
+    one = (np.array([5], np.uint32), np.array([0, len(k1)], np.int32), np.arange(len(k1), dtype=np.uint32)), (np.array([5], np.uint32), np.array([0, len(k2)], np.int32), np.arange(len(k2), dtype=np.uint32))
+    partner = oracle.search_by_bow(0, d1, k1["angle"], np.ones(len(k1), np.uint8), one[0], d2, k2["angle"], None, one[1], nnratio=0.9, check_ori=False)[1]
+    fv1, fv2 = _forced_partitions(len(k1), len(k2), rng, partner)[shape]
+    if shape == "edges":
+        assert np.diff(fv2[1])[:4].tolist() == [64, 65, 256, 257]
+    if shape == "one_sided":
+        assert len(set(fv1[0].tolist()) - set(fv2[0].tolist())) >= 3 and len(set(fv2[0].tolist()) - set(fv1[0].tolist())) >= 3
+    has1 = (rng.random(len(k1)) < 0.75).astype(np.uint8); bad1 = (rng.random(len(k1)) < 0.07).astype(np.uint8)
+    has2 = (rng.random(len(k2)) < 0.85).astype(np.uint8); bad2 = (rng.random(len(k2)) < 0.07).astype(np.uint8)
+    for mode in (0, 1):
+        n_r, m_r = ref.search_by_bow(mode, F[0], has1, bad1, fv1, F[1], has2, bad2, fv2, nnratio=0.8, check_ori=True)
+        v2 = (has2 & (1 - bad2)).astype(np.uint8) if mode == 1 else None
+        n_o, m_o = oracle.search_by_bow(mode, d1, k1["angle"], (has1 & (1 - bad1)).astype(np.uint8), fv1, d2, k2["angle"], v2, fv2, nnratio=0.8, check_ori=True)
+        assert n_r == n_o and np.array_equal(m_r, m_o), (shape, mode)
+        assert n_o > 20, (shape, mode, n_o)
+    par = oracle.OracleExtractor(n, 1.2, 8, 20, 7).params()
+    Fm = np.array([[0, -1e-3, 1.0 / 300], [1e-3, 0, -3.0 / 300], [-1.0 / 300, 3.0 / 300, 0]], np.float32) + rng.normal(0, 1e-5, (3, 3)).astype(np.float32)
+    t = np.array((0.3, 0.1, 1.0), np.float32)
+    free1 = (rng.random(len(k1)) < 0.3).astype(np.uint8); free2 = (rng.random(len(k2)) < 0.3).astype(np.uint8)
+    n_r, m_r = ref.search_for_triangulation(F[0], free1, fv1, F[1], free2, fv2, Fm, t, only_stereo=False, check_ori=True)
+    z1, z2 = np.zeros(len(k1), np.uint8), np.zeros(len(k2), np.uint8)
+    invz = np.float32(1.0) / t[2]
+    ex, ey = np.float32(1.0) * t[0] * invz + np.float32(0.0), np.float32(1.0) * t[1] * invz + np.float32(0.0)      # :667-669 with the pair's fx = fy = 1, cx = cy = 0
+    n_o, m_o = oracle.search_for_triangulation(d1, k1, free1, z1, fv1, d2, k2, free2, z2, fv2, Fm, ex, ey, par["scale_factors"], par["sigma2"], only_stereo=False, check_ori=True)
+    assert n_r == n_o and np.array_equal(m_r, m_o), shape
+    assert n_o > (10 if shape in ("one_node", "edges") else 0), (shape, n_o)      # (a node of 2 - 3 features offers a free feature little but its partner)
+
+
 def _world(rng, kl, w, h):
     nq = len(kl)
     X = (kl["x"] - 3.0 + rng.normal(0, 1.2, nq)).astype(np.float32); Y = (kl["y"] - 1.0 + rng.normal(0, 1.2, nq)).astype(np.float32)
