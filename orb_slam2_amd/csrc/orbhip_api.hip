@@ -89,7 +89,6 @@ extern "C" void orbhip_thread_release(void)
     g_hstage = nullptr; g_hstage_bytes = 0;
     if (g_nn_ws) { (void)hipSetDevice(g_nn_ws_dev); (void)hipDeviceSynchronize(); (void)hipFree(g_nn_ws); }
     g_nn_ws = nullptr; g_nn_ws_bytes = 0; g_nn_ws_dev = -1; g_nn_ws_stream = nullptr;
-    orbhip_bow_thread_release();
     if (cur >= 0) (void)hipSetDevice(cur);
     (void)hipGetLastError();
 }

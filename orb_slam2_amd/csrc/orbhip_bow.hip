@@ -25,6 +25,7 @@
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <algorithm>
 #include <array>
@@ -310,6 +311,15 @@ __device__ __forceinline__ unsigned long long bm_argmin_mask(int d, unsigned lon
 
 // slot of a batched launch that block `block` belongs to: pref[s] = first block of slot s (ascending, pref[nslots] = grid size); uniform -> scalar loads
 __device__ __forceinline__ int bm_batch_slot(const int* pref, int nslots, int block) { int s = 0; while (s + 1 < nslots && block >= pref[s + 1]) s++; return s; }
+// a pair's parameter block through the scalar cache (scalar_ptr, orbhip_internal.h): the address is the same for every lane, the host wrote the block before the
+// launch and no kernel writes it.  Copied member by member from the constant address space, the block sits in SGPRs and its pointers are global ones, exactly
+// like a by-value kernel argument (fetched as plain dwords the pointers would be generic: flat loads, a 64-bit address per lane).
+template <typename T> __device__ __forceinline__ T param_block(const T* p)
+{
+    T v;
+    __builtin_memcpy(&v, scalar_ptr(p), sizeof(T));
+    return v;
+}
 
 // wave64 minimum with DPP row shifts / broadcasts (6 dependent VALU steps against the 9 ballots of bm_argmin_mask); result broadcast from lane 63
 __device__ __forceinline__ int bm_wave_min(int v)
@@ -462,15 +472,13 @@ __device__ __forceinline__ void bow_match_body(const BowMatchParams& P, int a, i
     }
 }
 
-__global__ __launch_bounds__(256) void k_bow_match(BowMatchParams P)
-{
-    bow_match_body(P, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
-}
-// several independent pairs in one launch (orbhip_search_by_bow_batch): the parameter blocks live in device memory
-__global__ __launch_bounds__(256) void k_bow_match_batch(const BowMatchParams* Ps, const int* pref, int npairs)
+// Every pair of a call in one launch (a single-pair entry point is a batch of one): the parameter blocks lie in device memory, written by the host before the
+// launch and only read here; pref[s] = first block of pair s.  The pair's block comes through the scalar cache (param_block), so the walk finds it in SGPRs.
+__global__ __launch_bounds__(256) void k_bow_match(const BowMatchParams* Ps, const int* pref, int npairs)
 {
     const int sl = bm_batch_slot(pref, npairs, blockIdx.x);
-    bow_match_body(Ps[sl], (blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    const BowMatchParams P = param_block(Ps + sl);
+    bow_match_body(P, __builtin_amdgcn_readfirstlane((blockIdx.x - pref[sl]) * 4 + (threadIdx.x >> 6)), threadIdx.x & 63);
 }
 
 // ComputeThreeMaxima (ORBmatcher.cc:1601-1642), rejection of the other bins (:262-285 / :629-652), nmatches
@@ -500,8 +508,11 @@ __device__ __forceinline__ void bow_finish_body(const BowMatchParams& P, int tid
     __syncthreads();
     if (tid == 0) *P.nmatches = s_cnt;
 }
-__global__ __launch_bounds__(256) void k_bow_match_finish(BowMatchParams P) { bow_finish_body(P, threadIdx.x); }
-__global__ __launch_bounds__(256) void k_bow_match_finish_batch(const BowMatchParams* Ps) { bow_finish_body(Ps[blockIdx.x], threadIdx.x); }
+// one workgroup per pair, of either matcher: a pair's block begins with its BowMatchParams (TriParams::M), `stride` bytes from the previous pair's
+__global__ __launch_bounds__(256) void k_bow_match_finish(const uint8_t* blocks, int stride)
+{
+    bow_finish_body(*reinterpret_cast<const BowMatchParams*>(blocks + (size_t)blockIdx.x * stride), threadIdx.x);
+}
 
 // ------------------------------------------------------------------------------------------------ SearchForTriangulation
 // ORBmatcher::SearchForTriangulation (ORBmatcher.cc:657-823) + CheckDistEpipolarLine (:140-157) on flat data: features of two
@@ -671,27 +682,20 @@ template <bool FC> __device__ __forceinline__ void bow_triangulate_body(const Tr
         }
     }
 }
-__global__ __launch_bounds__(256) void k_bow_triangulate(TriParams T)
-{
-    bow_triangulate_body<false>(T, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
-}
-// one key frame against several neighbours in one launch (orbhip_search_for_triangulation_batch)
-__global__ __launch_bounds__(256) void k_bow_triangulate_batch(const TriParams* Ts, const int* pref, int npairs)
+// one key frame against several neighbours in one launch, laid out like k_bow_match's
+__global__ __launch_bounds__(256) void k_bow_triangulate(const TriParams* Ts, const int* pref, int npairs)
 {
     const int sl = bm_batch_slot(pref, npairs, blockIdx.x);
-    bow_triangulate_body<false>(Ts[sl], (blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    const TriParams T = param_block(Ts + sl);
+    bow_triangulate_body<false>(T, __builtin_amdgcn_readfirstlane((blockIdx.x - pref[sl]) * 4 + (threadIdx.x >> 6)), threadIdx.x & 63);
 }
-// the same two with the fused forms (ORBHIP_FP_CONTRACT): kernels of their own, so that the canonical ones' code is what it was
-__global__ __launch_bounds__(256) void k_bow_triangulate_fc(TriParams T)
-{
-    bow_triangulate_body<true>(T, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
-}
-__global__ __launch_bounds__(256) void k_bow_triangulate_batch_fc(const TriParams* Ts, const int* pref, int npairs)
+// the same with the fused forms (ORBHIP_FP_CONTRACT): a kernel of its own, so that the canonical one's code is what it was
+__global__ __launch_bounds__(256) void k_bow_triangulate_fc(const TriParams* Ts, const int* pref, int npairs)
 {
     const int sl = bm_batch_slot(pref, npairs, blockIdx.x);
-    bow_triangulate_body<true>(Ts[sl], (blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    const TriParams T = param_block(Ts + sl);
+    bow_triangulate_body<true>(T, __builtin_amdgcn_readfirstlane((blockIdx.x - pref[sl]) * 4 + (threadIdx.x >> 6)), threadIdx.x & 63);
 }
-__global__ __launch_bounds__(256) void k_bow_triangulate_finish_batch(const TriParams* Ts) { bow_finish_body(Ts[blockIdx.x].M, threadIdx.x); }
 
 // ------------------------------------------------------------------------------------------------ host side
 // Workspace for nframes x cap features.  Grow-only (a transform per frame / key frame with a different feature count must not pay eleven
@@ -1044,55 +1048,181 @@ extern "C" double orbhip_voc_score(const orbhip_voc* v, const uint32_t* id1, con
     }
 }
 
-void orbhip_bow_thread_release() {}      // (the two matchers below live in the calling thread's arena, orbhip_internal.h: nothing of their own to give back)
+// ------------------------------------------------------------------------------------------------ SearchByBoW / SearchForTriangulation: host side (include/orbhip.h)
+// The back end calls these matchers in loops over neighbours / candidates (Tracking.cc:1357-1380, LoopClosing.cc:239-375, LocalMapping.cc:237-268); a call is
+// launch latency, not work.  So the unit of work is a LIST of pairs, and a single-pair entry point hands in a list of one: every distinct side is laid out in the
+// thread's arena once, all pairs run in ONE launch set (the parameter blocks in device memory, a prefix table from block to pair), ONE copy up (the -1 / 0 initial
+// values of the outputs included), ONE copy down, on the thread's own stream.  The entry points validate, reset the outputs and name the pairs with work (PairJob);
+// bow_pairs_run does the rest for either matcher.
+namespace {
+struct SideDev { uint8_t *d = nullptr, *flag = nullptr, *st = nullptr; float *key = nullptr, *sc = nullptr, *sg = nullptr; uint32_t *fn = nullptr, *ff = nullptr; int* fo = nullptr; int n = 0, nfv = 0; bool second = false; };
+struct PairDev { int *m12 = nullptr, *bin = nullptr, *hist = nullptr; int tail[ORBHIP_HISTO_LENGTH + 2] = {0}; };      // a pair's outputs in the arena; tail: hist, nmatches, overflow as they come back
+struct PairJob { int s1, s2; int32_t* match12; int32_t* nmatches; const float* F12; float ex, ey; };      // a pair with work; s1, s2: its sides' places among the distinct ones
 
-// ORBmatcher::SearchByBoW on flat data; see include/orbhip.h.  Every array of the call is one block of the thread's arena: ONE copy up (the -1 / 0
-// initial values of the outputs included), two launches, ONE copy down, on the thread's own stream.
+// a side's arrays: descriptors, FeatureVector, then the angles and validity flags (SearchByBoW; `ones` where mode 0 has no flags for side 2) or the key points,
+// map-point and stereo flags and - of a side that is some pair's second - the level tables (SearchForTriangulation)
+template <typename Side> void side_layout(Arena& A, SideDev& D, const Side& s, const uint8_t* ones)
+{
+    const int n = s.n, m = s.fv_off[s.nfv];
+    D.n = n; D.nfv = s.nfv;
+    A.io(&D.d, (size_t)n * 32, s.desc, (size_t)n * 32);
+    A.io(&D.fn, s.nfv, s.fv_node, s.nfv); A.io(&D.fo, s.nfv + 1, (const int*)s.fv_off, s.nfv + 1); A.io(&D.ff, std::max(m, 1), s.fv_feat, m);
+    if constexpr (std::is_same<Side, orbhip_tri_side>::value) {
+        A.io(&D.key, (size_t)n * 4, s.kp, (size_t)n * 4); A.io(&D.flag, n, s.has_mp, n); A.io(&D.st, n, s.stereo, n);
+        if (D.second) { A.io(&D.sc, s.nlevels, s.scale_factors, s.nlevels); A.io(&D.sg, s.nlevels, s.level_sigma2, s.nlevels); }
+    } else {
+        A.io(&D.key, n, s.angle, n); A.io(&D.flag, n, s.valid ? s.valid : ones, n);
+    }
+}
+// the BowMatchParams part of a pair's block (ang1 / ang2: the key points' start in a triangulation block, which reads them as TriParams::kp1 / kp2)
+void bow_fill(BowMatchParams& P, const SideDev& a, const SideDev& b, int* match12, int* bin12, int* hist)
+{
+    P.d1 = a.d; P.ang1 = a.key; P.valid1 = a.flag; P.n1 = a.n; P.fn1 = a.fn; P.fo1 = a.fo; P.ff1 = a.ff; P.nf1 = a.nfv;
+    P.d2 = b.d; P.ang2 = b.key; P.valid2 = b.flag; P.n2 = b.n; P.fn2 = b.fn; P.fo2 = b.fo; P.ff2 = b.ff; P.nf2 = b.nfv;
+    P.match12 = match12; P.bin12 = bin12; P.hist = hist; P.nmatches = hist + ORBHIP_HISTO_LENGTH; P.overflow = P.nmatches + 1;
+}
+
+// Side = orbhip_bow_side: SearchByBoW(mode, nnratio, check_ori);  orbhip_tri_side: SearchForTriangulation(only_stereo, check_ori | ORBHIP_FP_CONTRACT).
+// Every job's match12 holds -1 and its nmatches 0 on entry; they hold that again after a HIP error or an overflowing node.
+template <typename Side> orbhip_status bow_pairs_run(const char* who, int device, const std::vector<const Side*>& sides, const std::vector<PairJob>& jobs, int mode, float nnratio, int check_ori, int only_stereo)
+{
+    constexpr bool TRI = std::is_same<Side, orbhip_tri_side>::value;
+    typedef typename std::conditional<TRI, TriParams, BowMatchParams>::type Params;
+    BOWCHK(hipSetDevice(device));
+    hipStream_t ts = orbhip_thread_stream(device);
+    const int NL = (int)jobs.size();
+    static const int zeros[ORBHIP_HISTO_LENGTH + 2] = {0};
+    std::vector<int> pref(NL + 1, 0);
+    std::vector<SideDev> D(sides.size());
+    std::vector<PairDev> O(NL);
+    std::vector<Params> hP(NL);
+    for (int k = 0; k < NL; k++) { pref[k + 1] = pref[k] + (sides[jobs[k].s1]->nfv + 3) / 4; D[jobs[k].s2].second = true; }
+    std::vector<uint8_t> ones;                                       // SearchByBoW's mode 0 ignores side 2's flags: a side may come without
+    if constexpr (!TRI) { int n = 0; for (const Side* sd : sides) if (!sd->valid) n = std::max(n, (int)sd->n); ones.assign(n, 1); }
+    Params* dP = nullptr; int* dpref = nullptr;
+    BOWCHK(arena_layout(device, [&](Arena& A) {
+        A.io(&dP, (size_t)NL, (const Params*)hP.data(), (size_t)NL);                         // (filled below, read when the arena is uploaded)
+        A.io(&dpref, (size_t)NL + 1, (const int*)pref.data(), (size_t)NL + 1);
+        for (size_t i = 0; i < sides.size(); i++) side_layout(A, D[i], *sides[i], ones.data());
+        for (int k = 0; k < NL; k++) { const int n1 = sides[jobs[k].s1]->n; A.io(&O[k].bin, n1, (const int*)jobs[k].match12, n1); }      // bin12 = -1 (match12 holds n1 of them)
+        // everything that travels back, of every pair, side by side behind the inputs: arena_download copies ONE span [first dst, last dst)
+        for (int k = 0; k < NL; k++) {
+            const int n1 = sides[jobs[k].s1]->n;
+            A.io(&O[k].m12, n1, (const int*)jobs[k].match12, n1, (int*)jobs[k].match12, n1);                                          // match12 = -1 in, the answer out
+            A.io(&O[k].hist, ORBHIP_HISTO_LENGTH + 2, zeros, ORBHIP_HISTO_LENGTH + 2, O[k].tail, ORBHIP_HISTO_LENGTH + 2);
+        }
+    }));
+    for (int k = 0; k < NL; k++) {
+        const PairJob& J = jobs[k]; const SideDev &a = D[J.s1], &b = D[J.s2];
+        memset(&hP[k], 0, sizeof hP[k]);
+        if constexpr (TRI) {
+            TriParams& T = hP[k];
+            bow_fill(T.M, a, b, O[k].m12, O[k].bin, O[k].hist);
+            T.M.check_ori = check_ori & ~ORBHIP_FP_CONTRACT;        // (the flag bit selects the fused kernel)
+            T.kp1 = a.key; T.kp2 = b.key; T.st1 = a.st; T.st2 = b.st;
+            for (int i = 0; i < 9; i++) T.F[i] = J.F12[i];
+            T.ex = J.ex; T.ey = J.ey; T.scale2 = b.sc; T.sigma2_2 = b.sg; T.only_stereo = only_stereo;
+        } else {
+            bow_fill(hP[k], a, b, O[k].m12, O[k].bin, O[k].hist);
+            hP[k].mode = mode; hP[k].nnratio = nnratio; hP[k].check_ori = check_ori;
+        }
+    }
+    hipError_t e = arena_upload(ts);
+    if (e == hipSuccess) {
+        if constexpr (TRI) hipLaunchKernelGGL(((check_ori & ORBHIP_FP_CONTRACT) ? k_bow_triangulate_fc : k_bow_triangulate), dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dP, (const int*)dpref, NL);
+        else hipLaunchKernelGGL(k_bow_match, dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const BowMatchParams*)dP, (const int*)dpref, NL);
+        hipLaunchKernelGGL(k_bow_match_finish, dim3(NL, 1, 1), dim3(256, 1, 1), 0, ts, (const uint8_t*)dP, (int)sizeof(Params));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = arena_download(ts);
+    bool overflow = false;                                           // (only SearchByBoW's walk ever reports one)
+    for (int k = 0; k < NL; k++) overflow = overflow || O[k].tail[ORBHIP_HISTO_LENGTH + 1] != 0;
+    if (e != hipSuccess || overflow) {
+        if (e != hipSuccess) (void)hipStreamSynchronize(ts);
+        for (const PairJob& J : jobs) std::fill_n(J.match12, sides[J.s1]->n, -1);
+        return e != hipSuccess ? orbhip_set_error(ORBHIP_ERR_HIP, "%s: %s", who, hipGetErrorString(e))
+                               : orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "a vocabulary node holds more than %d features of side 2", 64 * BM_CHUNKS);
+    }
+    for (int k = 0; k < NL; k++) *jobs[k].nmatches = O[k].tail[ORBHIP_HISTO_LENGTH];
+    if constexpr (TRI) ORBHIP_RECORD(for (const PairJob& J : jobs) {      // one record per pair
+        const orbhip_tri_side &a = *sides[J.s1], &b = *sides[J.s2];
+        TestRecord R(3); const float epi[2] = {J.ex, J.ey}; const int ipar[3] = {only_stereo, check_ori, *J.nmatches};
+        R.put(a.desc, (size_t)a.n * 32); R.put(a.kp, (size_t)a.n * 4); R.put(a.has_mp, a.n); R.put(a.stereo, a.n); R.put(a.fv_node, a.nfv); R.put(a.fv_off, (size_t)a.nfv + 1); R.put(a.fv_feat, a.fv_off[a.nfv]);
+        R.put(b.desc, (size_t)b.n * 32); R.put(b.kp, (size_t)b.n * 4); R.put(b.has_mp, b.n); R.put(b.stereo, b.n); R.put(b.fv_node, b.nfv); R.put(b.fv_off, (size_t)b.nfv + 1); R.put(b.fv_feat, b.fv_off[b.nfv]);
+        R.put(J.F12, 9); R.put(epi, 2); R.put(b.scale_factors, b.nlevels); R.put(b.level_sigma2, b.nlevels); R.put(ipar, 3); R.put(J.match12, a.n);
+    });
+    return ORBHIP_OK;
+}
+
+// npairs independent SearchByBoW calls; sides are recognised by pointer
+orbhip_status search_by_bow_pairs(const char* who, int device, int mode, int npairs, orbhip_bow_pair* pairs, float nnratio, int check_ori)
+{
+    if (npairs < 0 || (npairs > 0 && !pairs) || (mode != 0 && mode != 1)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::vector<const orbhip_bow_side*> sides;                       // distinct sides, in order of first use
+    std::vector<PairJob> jobs;
+    auto side_index = [&](const orbhip_bow_side* sd) { for (size_t i = 0; i < sides.size(); i++) if (sides[i] == sd) return (int)i; sides.push_back(sd); return (int)sides.size() - 1; };
+    for (int p = 0; p < npairs; p++) {
+        orbhip_bow_pair& Q = pairs[p];
+        if (!Q.side1 || !Q.side2 || Q.side1->n < 0 || (Q.side1->n > 0 && !Q.match12) || Q.side2->n < 0 || Q.side1->nfv < 0 || Q.side2->nfv < 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument in pair %d", p);
+        Q.nmatches = 0;
+        std::fill_n(Q.match12, Q.side1->n, -1);
+        if (Q.side1->n == 0 || Q.side2->n == 0 || Q.side1->nfv == 0 || Q.side2->nfv == 0) continue;
+        for (const orbhip_bow_side* sd : {Q.side1, Q.side2})
+            if (!sd->desc || !sd->angle || !sd->fv_node || !sd->fv_off || !sd->fv_feat) return orbhip_set_error(ORBHIP_ERR_INVALID, "null array in pair %d", p);
+        if (!Q.side1->valid || (mode == 1 && !Q.side2->valid)) return orbhip_set_error(ORBHIP_ERR_INVALID, "null validity flags in pair %d", p);
+        jobs.push_back(PairJob{side_index(Q.side1), side_index(Q.side2), Q.match12, &Q.nmatches, nullptr, 0.f, 0.f});
+    }
+    return jobs.empty() ? ORBHIP_OK : bow_pairs_run(who, device, sides, jobs, mode, nnratio, check_ori, 0);
+}
+
+// SearchForTriangulation of one key frame against npairs neighbours; every neighbour is a side of its own
+orbhip_status search_for_triangulation_pairs(const char* who, int device, const orbhip_tri_side* kf1, int npairs, orbhip_tri_pair* pairs, int only_stereo, int check_ori)
+{
+    if (!kf1 || npairs < 0 || (npairs > 0 && !pairs) || kf1->n < 0 || kf1->nfv < 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::vector<const orbhip_tri_side*> sides(1, kf1);
+    std::vector<PairJob> jobs;
+    for (int p = 0; p < npairs; p++) {
+        orbhip_tri_pair& Q = pairs[p];
+        if (!Q.kf2 || (kf1->n > 0 && !Q.match12) || Q.kf2->n < 0 || Q.kf2->nfv < 0 || Q.kf2->nlevels < 1) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument in pair %d", p);
+        Q.nmatches = 0;
+        std::fill_n(Q.match12, kf1->n, -1);
+        if (kf1->n == 0 || Q.kf2->n == 0 || kf1->nfv == 0 || Q.kf2->nfv == 0) continue;
+        const orbhip_tri_side& b = *Q.kf2;
+        if (!b.desc || !b.kp || !b.has_mp || !b.stereo || !b.fv_node || !b.fv_off || !b.fv_feat || !b.scale_factors || !b.level_sigma2) return orbhip_set_error(ORBHIP_ERR_INVALID, "null array in pair %d", p);
+        sides.push_back(Q.kf2);
+        jobs.push_back(PairJob{0, (int)sides.size() - 1, Q.match12, &Q.nmatches, Q.F12, Q.ex, Q.ey});
+    }
+    if (jobs.empty()) return ORBHIP_OK;
+    if (!kf1->desc || !kf1->kp || !kf1->has_mp || !kf1->stereo || !kf1->fv_node || !kf1->fv_off || !kf1->fv_feat) return orbhip_set_error(ORBHIP_ERR_INVALID, "null array in key frame 1");
+    return bow_pairs_run(who, device, sides, jobs, 0, 0.f, check_ori, only_stereo);
+}
+}
+
+extern "C" orbhip_status orbhip_search_by_bow_batch(int device, int mode, int npairs, orbhip_bow_pair* pairs, float nnratio, int check_ori)
+{
+    OrbApiTimer api_timer;
+    return search_by_bow_pairs("search_by_bow_batch", device, mode, npairs, pairs, nnratio, check_ori);
+}
+
+extern "C" orbhip_status orbhip_search_for_triangulation_batch(int device, const orbhip_tri_side* kf1, int npairs, orbhip_tri_pair* pairs, int only_stereo, int check_ori)
+{
+    OrbApiTimer api_timer;
+    return search_for_triangulation_pairs("search_for_triangulation_batch", device, kf1, npairs, pairs, only_stereo, check_ori);
+}
+
+// ORBmatcher::SearchByBoW on flat data; see include/orbhip.h
 extern "C" orbhip_status orbhip_search_by_bow(int device, int mode,
     const uint8_t* desc1, const float* angle1, const uint8_t* valid1, int n1, const uint32_t* fv1_node, const int32_t* fv1_off, const uint32_t* fv1_feat, int nfv1,
     const uint8_t* desc2, const float* angle2, const uint8_t* valid2, int n2, const uint32_t* fv2_node, const int32_t* fv2_off, const uint32_t* fv2_feat, int nfv2,
     float nnratio, int check_ori, int32_t* match12, int* nmatches)
 {
     OrbApiTimer api_timer;
-    if (!match12 || !nmatches || n1 < 0 || n2 < 0 || nfv1 < 0 || nfv2 < 0 || (mode != 0 && mode != 1)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
-    *nmatches = 0;
-    for (int i = 0; i < n1; i++) match12[i] = -1;
-    if (n1 == 0 || n2 == 0 || nfv1 == 0 || nfv2 == 0) return ORBHIP_OK;
-    if (!desc1 || !desc2 || !angle1 || !angle2 || !valid1 || !fv1_node || !fv1_off || !fv1_feat || !fv2_node || !fv2_off || !fv2_feat || (mode == 1 && !valid2))
-        return orbhip_set_error(ORBHIP_ERR_INVALID, "null argument");
-    BOWCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    const int m1 = fv1_off[nfv1], m2 = fv2_off[nfv2];
-    std::vector<uint8_t> ones;
-    if (!valid2) { ones.assign(n2, 1); valid2 = ones.data(); }
-    BowMatchParams P; memset(&P, 0, sizeof P);
-    int zeros[ORBHIP_HISTO_LENGTH + 2] = {0}, tail[ORBHIP_HISTO_LENGTH + 2] = {0};
-    uint8_t *d1 = nullptr, *d2 = nullptr, *v1 = nullptr, *v2 = nullptr; float *a1 = nullptr, *a2 = nullptr; uint32_t *fn1 = nullptr, *ff1 = nullptr, *fn2 = nullptr, *ff2 = nullptr;
-    int *fo1 = nullptr, *fo2 = nullptr, *m12 = nullptr, *bin12 = nullptr, *hist = nullptr;
-    BOWCHK(arena_layout(device, [&](Arena& A) {
-        A.io(&d1, (size_t)n1 * 32, desc1, (size_t)n1 * 32); A.io(&a1, n1, angle1, n1); A.io(&v1, n1, valid1, n1);
-        A.io(&fn1, nfv1, fv1_node, nfv1); A.io(&fo1, nfv1 + 1, (const int*)fv1_off, nfv1 + 1); A.io(&ff1, std::max(m1, 1), fv1_feat, m1);
-        A.io(&d2, (size_t)n2 * 32, desc2, (size_t)n2 * 32); A.io(&a2, n2, angle2, n2); A.io(&v2, n2, valid2, n2);
-        A.io(&fn2, nfv2, fv2_node, nfv2); A.io(&fo2, nfv2 + 1, (const int*)fv2_off, nfv2 + 1); A.io(&ff2, std::max(m2, 1), fv2_feat, m2);
-        A.io(&bin12, n1, (const int*)match12, n1);                                        // bin12 = -1 (match12 holds n1 of them)
-        A.io(&m12, n1, (const int*)match12, n1, (int*)match12, n1);                       // match12 = -1 in, the answer out
-        A.io(&hist, ORBHIP_HISTO_LENGTH + 2, (const int*)zeros, ORBHIP_HISTO_LENGTH + 2, tail, ORBHIP_HISTO_LENGTH + 2);      // hist, nmatches, overflow
-    }));
-    hipError_t e = arena_upload(ts);
-    if (e == hipSuccess) {
-        P.mode = mode; P.nnratio = nnratio; P.check_ori = check_ori;
-        P.d1 = d1; P.ang1 = a1; P.valid1 = v1; P.n1 = n1; P.fn1 = fn1; P.fo1 = fo1; P.ff1 = ff1; P.nf1 = nfv1;
-        P.d2 = d2; P.ang2 = a2; P.valid2 = v2; P.n2 = n2; P.fn2 = fn2; P.fo2 = fo2; P.ff2 = ff2; P.nf2 = nfv2;
-        P.match12 = m12; P.bin12 = bin12; P.hist = hist; P.nmatches = hist + ORBHIP_HISTO_LENGTH; P.overflow = P.nmatches + 1;
-        hipLaunchKernelGGL(k_bow_match, dim3((nfv1 + 3) / 4, 1, 1), dim3(256, 1, 1), 0, ts, P);
-        hipLaunchKernelGGL(k_bow_match_finish, dim3(1, 1, 1), dim3(256, 1, 1), 0, ts, P);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = arena_download(ts);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ts); for (int i = 0; i < n1; i++) match12[i] = -1; return orbhip_set_error(ORBHIP_ERR_HIP, "search_by_bow: %s", hipGetErrorString(e)); }
-    if (tail[ORBHIP_HISTO_LENGTH + 1]) { for (int i = 0; i < n1; i++) match12[i] = -1; return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "a vocabulary node holds more than %d features of side 2", 64 * BM_CHUNKS); }
-    *nmatches = tail[ORBHIP_HISTO_LENGTH];
-    return ORBHIP_OK;
+    if (!match12 || !nmatches) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    const orbhip_bow_side s1 = {desc1, angle1, valid1, n1, fv1_node, fv1_off, fv1_feat, nfv1}, s2 = {desc2, angle2, valid2, n2, fv2_node, fv2_off, fv2_feat, nfv2};
+    orbhip_bow_pair Q = {&s1, &s2, match12, 0};
+    const orbhip_status st = search_by_bow_pairs("search_by_bow", device, mode, 1, &Q, nnratio, check_ori);
+    *nmatches = Q.nmatches;
+    return st;
 }
 
 // ORBmatcher::SearchForTriangulation on flat data; see include/orbhip.h
@@ -1103,217 +1233,12 @@ extern "C" orbhip_status orbhip_search_for_triangulation(int device,
     int32_t* match12, int* nmatches)
 {
     OrbApiTimer api_timer;
-    if (!match12 || !nmatches || n1 < 0 || n2 < 0 || nfv1 < 0 || nfv2 < 0 || nlevels2 < 1) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
-    *nmatches = 0;
-    for (int i = 0; i < n1; i++) match12[i] = -1;
-    if (n1 == 0 || n2 == 0 || nfv1 == 0 || nfv2 == 0) return ORBHIP_OK;
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !has_mp1 || !has_mp2 || !stereo1 || !stereo2 || !fv1_node || !fv1_off || !fv1_feat || !fv2_node || !fv2_off || !fv2_feat ||
-        !F12 || !scale_factors2 || !level_sigma2_2) return orbhip_set_error(ORBHIP_ERR_INVALID, "null argument");
-    BOWCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    const int m1 = fv1_off[nfv1], m2 = fv2_off[nfv2];
-    int zeros[ORBHIP_HISTO_LENGTH + 2] = {0}, tail[ORBHIP_HISTO_LENGTH + 2] = {0};
-    uint8_t *d1 = nullptr, *d2 = nullptr, *h1 = nullptr, *h2 = nullptr, *s1 = nullptr, *s2 = nullptr; float *k1 = nullptr, *k2 = nullptr, *sc2 = nullptr, *sg2 = nullptr;
-    uint32_t *fn1 = nullptr, *ff1 = nullptr, *fn2 = nullptr, *ff2 = nullptr; int *fo1 = nullptr, *fo2 = nullptr, *m12 = nullptr, *bin12 = nullptr, *hist = nullptr;
-    BOWCHK(arena_layout(device, [&](Arena& A) {
-        A.io(&d1, (size_t)n1 * 32, desc1, (size_t)n1 * 32); A.io(&k1, (size_t)n1 * 4, kp1, (size_t)n1 * 4); A.io(&h1, n1, has_mp1, n1); A.io(&s1, n1, stereo1, n1);
-        A.io(&fn1, nfv1, fv1_node, nfv1); A.io(&fo1, nfv1 + 1, (const int*)fv1_off, nfv1 + 1); A.io(&ff1, std::max(m1, 1), fv1_feat, m1);
-        A.io(&d2, (size_t)n2 * 32, desc2, (size_t)n2 * 32); A.io(&k2, (size_t)n2 * 4, kp2, (size_t)n2 * 4); A.io(&h2, n2, has_mp2, n2); A.io(&s2, n2, stereo2, n2);
-        A.io(&fn2, nfv2, fv2_node, nfv2); A.io(&fo2, nfv2 + 1, (const int*)fv2_off, nfv2 + 1); A.io(&ff2, std::max(m2, 1), fv2_feat, m2);
-        A.io(&sc2, nlevels2, scale_factors2, nlevels2); A.io(&sg2, nlevels2, level_sigma2_2, nlevels2);
-        A.io(&bin12, n1, (const int*)match12, n1);
-        A.io(&m12, n1, (const int*)match12, n1, (int*)match12, n1);
-        A.io(&hist, ORBHIP_HISTO_LENGTH + 2, (const int*)zeros, ORBHIP_HISTO_LENGTH + 2, tail, ORBHIP_HISTO_LENGTH + 2);
-    }));
-    hipError_t e = arena_upload(ts);
-    if (e == hipSuccess) {
-        TriParams T; memset(&T, 0, sizeof T);
-        BowMatchParams& P = T.M;
-        P.mode = 0; P.nnratio = 0.f; P.check_ori = check_ori & ~ORBHIP_FP_CONTRACT;      // (the flag bit selects the fused kernel)
-        P.d1 = d1; P.valid1 = h1; P.n1 = n1; P.fn1 = fn1; P.fo1 = fo1; P.ff1 = ff1; P.nf1 = nfv1;
-        P.d2 = d2; P.valid2 = h2; P.n2 = n2; P.fn2 = fn2; P.fo2 = fo2; P.ff2 = ff2; P.nf2 = nfv2;
-        P.match12 = m12; P.bin12 = bin12; P.hist = hist; P.nmatches = hist + ORBHIP_HISTO_LENGTH; P.overflow = P.nmatches + 1;
-        T.kp1 = k1; T.kp2 = k2; T.st1 = s1; T.st2 = s2;
-        for (int i = 0; i < 9; i++) T.F[i] = F12[i];
-        T.ex = ex; T.ey = ey; T.scale2 = sc2; T.sigma2_2 = sg2; T.only_stereo = only_stereo;
-        if (check_ori & ORBHIP_FP_CONTRACT) hipLaunchKernelGGL(k_bow_triangulate_fc, dim3((nfv1 + 3) / 4, 1, 1), dim3(256, 1, 1), 0, ts, T);
-        else hipLaunchKernelGGL(k_bow_triangulate, dim3((nfv1 + 3) / 4, 1, 1), dim3(256, 1, 1), 0, ts, T);
-        hipLaunchKernelGGL(k_bow_match_finish, dim3(1, 1, 1), dim3(256, 1, 1), 0, ts, P);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = arena_download(ts);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ts); for (int i = 0; i < n1; i++) match12[i] = -1; return orbhip_set_error(ORBHIP_ERR_HIP, "search_for_triangulation: %s", hipGetErrorString(e)); }
-    *nmatches = tail[ORBHIP_HISTO_LENGTH];
-    ORBHIP_RECORD(
-        TestRecord R(3); const float epi[2] = {ex, ey}; const int ipar[3] = {only_stereo, check_ori, *nmatches};
-        R.put(desc1, (size_t)n1 * 32); R.put(kp1, (size_t)n1 * 4); R.put(has_mp1, n1); R.put(stereo1, n1); R.put(fv1_node, nfv1); R.put(fv1_off, (size_t)nfv1 + 1); R.put(fv1_feat, m1);
-        R.put(desc2, (size_t)n2 * 32); R.put(kp2, (size_t)n2 * 4); R.put(has_mp2, n2); R.put(stereo2, n2); R.put(fv2_node, nfv2); R.put(fv2_off, (size_t)nfv2 + 1); R.put(fv2_feat, m2);
-        R.put(F12, 9); R.put(epi, 2); R.put(scale_factors2, nlevels2); R.put(level_sigma2_2, nlevels2); R.put(ipar, 3); R.put(match12, n1);
-    );
-    return ORBHIP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ batched forms (include/orbhip.h)
-// The back end calls these matchers in loops over neighbours / candidates (Tracking.cc:1357-1380, LoopClosing.cc:239-375,
-// LocalMapping.cc:237-268); a call is launch latency, not work.  Here every distinct side travels once, all pairs run in ONE launch set (the
-// parameter blocks in device memory, a prefix table from block to pair) and all answers come back in one copy.
-namespace {
-struct SideDev { uint8_t* d = nullptr; float* ang = nullptr; uint8_t* valid = nullptr; uint32_t* fn = nullptr; int* fo = nullptr; uint32_t* ff = nullptr; };
-}
-extern "C" orbhip_status orbhip_search_by_bow_batch(int device, int mode, int npairs, orbhip_bow_pair* pairs, float nnratio, int check_ori)
-{
-    OrbApiTimer api_timer;
-    if (npairs < 0 || (npairs > 0 && !pairs) || (mode != 0 && mode != 1)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
-    std::vector<const orbhip_bow_side*> sides;                       // distinct sides, in order of first use
-    std::vector<int> live;                                           // pairs with work
-    auto side_index = [&](const orbhip_bow_side* sd) { for (size_t i = 0; i < sides.size(); i++) if (sides[i] == sd) return (int)i; sides.push_back(sd); return (int)sides.size() - 1; };
-    for (int p = 0; p < npairs; p++) {
-        orbhip_bow_pair& Q = pairs[p];
-        if (!Q.side1 || !Q.side2 || Q.side1->n < 0 || (Q.side1->n > 0 && !Q.match12) || Q.side2->n < 0 || Q.side1->nfv < 0 || Q.side2->nfv < 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument in pair %d", p);
-        Q.nmatches = 0;
-        for (int i = 0; i < Q.side1->n; i++) Q.match12[i] = -1;
-        if (Q.side1->n == 0 || Q.side2->n == 0 || Q.side1->nfv == 0 || Q.side2->nfv == 0) continue;
-        for (const orbhip_bow_side* sd : {Q.side1, Q.side2})
-            if (!sd->desc || !sd->angle || !sd->fv_node || !sd->fv_off || !sd->fv_feat) return orbhip_set_error(ORBHIP_ERR_INVALID, "null array in pair %d", p);
-        if (!Q.side1->valid || (mode == 1 && !Q.side2->valid)) return orbhip_set_error(ORBHIP_ERR_INVALID, "null validity flags in pair %d", p);
-        live.push_back(p);
-    }
-    if (live.empty()) return ORBHIP_OK;
-    BOWCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    const int NL = (int)live.size();
-    std::vector<int> s1(NL), s2(NL), pref(NL + 1, 0);
-    for (int k = 0; k < NL; k++) { s1[k] = side_index(pairs[live[k]].side1); s2[k] = side_index(pairs[live[k]].side2); pref[k + 1] = pref[k] + (pairs[live[k]].side1->nfv + 3) / 4; }
-    int nmax2 = 1; for (const orbhip_bow_side* sd : sides) nmax2 = std::max(nmax2, sd->n);
-    const std::vector<uint8_t> ones(nmax2, 1);                       // mode 0 ignores side 2's flags
-    std::vector<SideDev> D(sides.size());
-    std::vector<BowMatchParams> hP(NL);
-    std::vector<std::array<int, ORBHIP_HISTO_LENGTH + 2>> zeros(NL), tail(NL);
-    for (auto& z : zeros) z.fill(0);
-    BowMatchParams* dP = nullptr; int* dpref = nullptr;
-    std::vector<int*> dm12(NL), dbin(NL), dhist(NL);
-    BOWCHK(arena_layout(device, [&](Arena& A) {
-        A.io(&dP, (size_t)NL, (const BowMatchParams*)hP.data(), (size_t)NL);                 // (filled below, read when the arena is uploaded)
-        A.io(&dpref, (size_t)NL + 1, (const int*)pref.data(), (size_t)NL + 1);
-        for (size_t i = 0; i < sides.size(); i++) {
-            const orbhip_bow_side& sd = *sides[i]; const int m = sd.fv_off[sd.nfv];
-            A.io(&D[i].d, (size_t)sd.n * 32, sd.desc, (size_t)sd.n * 32); A.io(&D[i].ang, sd.n, sd.angle, sd.n);
-            A.io(&D[i].valid, sd.n, sd.valid ? sd.valid : ones.data(), sd.n);
-            A.io(&D[i].fn, sd.nfv, sd.fv_node, sd.nfv); A.io(&D[i].fo, sd.nfv + 1, (const int*)sd.fv_off, sd.nfv + 1); A.io(&D[i].ff, std::max(m, 1), sd.fv_feat, m);
-        }
-        for (int k = 0; k < NL; k++) {
-            orbhip_bow_pair& Q = pairs[live[k]]; const int n1 = Q.side1->n;
-            A.io(&dbin[k], n1, (const int*)Q.match12, n1);                                   // bin12 = -1
-            A.io(&dm12[k], n1, (const int*)Q.match12, n1, (int*)Q.match12, n1);             // match12 = -1 in, the answer out
-            A.io(&dhist[k], ORBHIP_HISTO_LENGTH + 2, (const int*)zeros[k].data(), ORBHIP_HISTO_LENGTH + 2, tail[k].data(), ORBHIP_HISTO_LENGTH + 2);
-        }
-    }));
-    for (int k = 0; k < NL; k++) {
-        const orbhip_bow_pair& Q = pairs[live[k]]; BowMatchParams& P = hP[k]; memset(&P, 0, sizeof P);
-        const SideDev &a = D[s1[k]], &b = D[s2[k]];
-        P.mode = mode; P.nnratio = nnratio; P.check_ori = check_ori;
-        P.d1 = a.d; P.ang1 = a.ang; P.valid1 = a.valid; P.n1 = Q.side1->n; P.fn1 = a.fn; P.fo1 = a.fo; P.ff1 = a.ff; P.nf1 = Q.side1->nfv;
-        P.d2 = b.d; P.ang2 = b.ang; P.valid2 = b.valid; P.n2 = Q.side2->n; P.fn2 = b.fn; P.fo2 = b.fo; P.ff2 = b.ff; P.nf2 = Q.side2->nfv;
-        P.match12 = dm12[k]; P.bin12 = dbin[k]; P.hist = dhist[k]; P.nmatches = dhist[k] + ORBHIP_HISTO_LENGTH; P.overflow = P.nmatches + 1;
-    }
-    hipError_t e = arena_upload(ts);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_bow_match_batch, dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const BowMatchParams*)dP, (const int*)dpref, NL);
-        hipLaunchKernelGGL(k_bow_match_finish_batch, dim3(NL, 1, 1), dim3(256, 1, 1), 0, ts, (const BowMatchParams*)dP);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = arena_download(ts);
-    bool overflow = false;
-    for (int k = 0; k < NL; k++) overflow = overflow || tail[k][ORBHIP_HISTO_LENGTH + 1] != 0;
-    if (e != hipSuccess || overflow) {
-        if (e != hipSuccess) (void)hipStreamSynchronize(ts);
-        for (int k = 0; k < NL; k++) { orbhip_bow_pair& Q = pairs[live[k]]; for (int i = 0; i < Q.side1->n; i++) Q.match12[i] = -1; }
-        return e != hipSuccess ? orbhip_set_error(ORBHIP_ERR_HIP, "search_by_bow_batch: %s", hipGetErrorString(e))
-                               : orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "a vocabulary node holds more than %d features of side 2", 64 * BM_CHUNKS);
-    }
-    for (int k = 0; k < NL; k++) pairs[live[k]].nmatches = tail[k][ORBHIP_HISTO_LENGTH];
-    return ORBHIP_OK;
-}
-
-extern "C" orbhip_status orbhip_search_for_triangulation_batch(int device, const orbhip_tri_side* kf1, int npairs, orbhip_tri_pair* pairs, int only_stereo, int check_ori)
-{
-    OrbApiTimer api_timer;
-    if (!kf1 || npairs < 0 || (npairs > 0 && !pairs) || kf1->n < 0 || kf1->nfv < 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
-    std::vector<int> live;
-    for (int p = 0; p < npairs; p++) {
-        orbhip_tri_pair& Q = pairs[p];
-        if (!Q.kf2 || (kf1->n > 0 && !Q.match12) || Q.kf2->n < 0 || Q.kf2->nfv < 0 || Q.kf2->nlevels < 1) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument in pair %d", p);
-        Q.nmatches = 0;
-        for (int i = 0; i < kf1->n; i++) Q.match12[i] = -1;
-        if (kf1->n == 0 || Q.kf2->n == 0 || kf1->nfv == 0 || Q.kf2->nfv == 0) continue;
-        const orbhip_tri_side& b = *Q.kf2;
-        if (!b.desc || !b.kp || !b.has_mp || !b.stereo || !b.fv_node || !b.fv_off || !b.fv_feat || !b.scale_factors || !b.level_sigma2) return orbhip_set_error(ORBHIP_ERR_INVALID, "null array in pair %d", p);
-        live.push_back(p);
-    }
-    if (live.empty()) return ORBHIP_OK;
-    if (!kf1->desc || !kf1->kp || !kf1->has_mp || !kf1->stereo || !kf1->fv_node || !kf1->fv_off || !kf1->fv_feat) return orbhip_set_error(ORBHIP_ERR_INVALID, "null array in key frame 1");
-    BOWCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    const int NL = (int)live.size(), n1 = kf1->n, m1 = kf1->fv_off[kf1->nfv], blocks1 = (kf1->nfv + 3) / 4;
-    std::vector<int> pref(NL + 1, 0);
-    for (int k = 0; k < NL; k++) pref[k + 1] = pref[k] + blocks1;
-    std::vector<TriParams> hT(NL);
-    std::vector<std::array<int, ORBHIP_HISTO_LENGTH + 2>> zeros(NL), tail(NL);
-    for (auto& z : zeros) z.fill(0);
-    TriParams* dT = nullptr; int* dpref = nullptr;
-    uint8_t *d1 = nullptr, *h1 = nullptr, *st1 = nullptr; float* k1 = nullptr; uint32_t *fn1 = nullptr, *ff1 = nullptr; int* fo1 = nullptr;
-    struct Side2 { uint8_t *d, *h, *st; float *k, *sc, *sg; uint32_t *fn, *ff; int* fo; };
-    std::vector<Side2> B(NL); std::vector<int*> dm12(NL), dbin(NL), dhist(NL);
-    BOWCHK(arena_layout(device, [&](Arena& A) {
-        A.io(&dT, (size_t)NL, (const TriParams*)hT.data(), (size_t)NL);
-        A.io(&dpref, (size_t)NL + 1, (const int*)pref.data(), (size_t)NL + 1);
-        A.io(&d1, (size_t)n1 * 32, kf1->desc, (size_t)n1 * 32); A.io(&k1, (size_t)n1 * 4, kf1->kp, (size_t)n1 * 4); A.io(&h1, n1, kf1->has_mp, n1); A.io(&st1, n1, kf1->stereo, n1);
-        A.io(&fn1, kf1->nfv, kf1->fv_node, kf1->nfv); A.io(&fo1, kf1->nfv + 1, (const int*)kf1->fv_off, kf1->nfv + 1); A.io(&ff1, std::max(m1, 1), kf1->fv_feat, m1);
-        for (int k = 0; k < NL; k++) {
-            orbhip_tri_pair& Q = pairs[live[k]]; const orbhip_tri_side& b = *Q.kf2; const int n2 = b.n, m2 = b.fv_off[b.nfv]; Side2& S = B[k];
-            A.io(&S.d, (size_t)n2 * 32, b.desc, (size_t)n2 * 32); A.io(&S.k, (size_t)n2 * 4, b.kp, (size_t)n2 * 4); A.io(&S.h, n2, b.has_mp, n2); A.io(&S.st, n2, b.stereo, n2);
-            A.io(&S.fn, b.nfv, b.fv_node, b.nfv); A.io(&S.fo, b.nfv + 1, (const int*)b.fv_off, b.nfv + 1); A.io(&S.ff, std::max(m2, 1), b.fv_feat, m2);
-            A.io(&S.sc, b.nlevels, b.scale_factors, b.nlevels); A.io(&S.sg, b.nlevels, b.level_sigma2, b.nlevels);
-            A.io(&dbin[k], n1, (const int*)Q.match12, n1);
-        }
-        // everything that travels back, of every pair, side by side behind the inputs: arena_download copies ONE span [first dst, last dst)
-        for (int k = 0; k < NL; k++) {
-            orbhip_tri_pair& Q = pairs[live[k]];
-            A.io(&dm12[k], n1, (const int*)Q.match12, n1, (int*)Q.match12, n1);
-            A.io(&dhist[k], ORBHIP_HISTO_LENGTH + 2, (const int*)zeros[k].data(), ORBHIP_HISTO_LENGTH + 2, tail[k].data(), ORBHIP_HISTO_LENGTH + 2);
-        }
-    }));
-    for (int k = 0; k < NL; k++) {
-        const orbhip_tri_pair& Q = pairs[live[k]]; const Side2& S = B[k]; TriParams& T = hT[k]; memset(&T, 0, sizeof T);
-        BowMatchParams& P = T.M;
-        P.mode = 0; P.nnratio = 0.f; P.check_ori = check_ori & ~ORBHIP_FP_CONTRACT;      // (the flag bit selects the fused kernel)
-        P.d1 = d1; P.valid1 = h1; P.n1 = n1; P.fn1 = fn1; P.fo1 = fo1; P.ff1 = ff1; P.nf1 = kf1->nfv;
-        P.d2 = S.d; P.valid2 = S.h; P.n2 = Q.kf2->n; P.fn2 = S.fn; P.fo2 = S.fo; P.ff2 = S.ff; P.nf2 = Q.kf2->nfv;
-        P.match12 = dm12[k]; P.bin12 = dbin[k]; P.hist = dhist[k]; P.nmatches = dhist[k] + ORBHIP_HISTO_LENGTH; P.overflow = P.nmatches + 1;
-        T.kp1 = k1; T.kp2 = S.k; T.st1 = st1; T.st2 = S.st;
-        for (int i = 0; i < 9; i++) T.F[i] = Q.F12[i];
-        T.ex = Q.ex; T.ey = Q.ey; T.scale2 = S.sc; T.sigma2_2 = S.sg; T.only_stereo = only_stereo;
-    }
-    hipError_t e = arena_upload(ts);
-    if (e == hipSuccess) {
-        if (check_ori & ORBHIP_FP_CONTRACT) hipLaunchKernelGGL(k_bow_triangulate_batch_fc, dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dT, (const int*)dpref, NL);
-        else hipLaunchKernelGGL(k_bow_triangulate_batch, dim3(pref[NL], 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dT, (const int*)dpref, NL);
-        hipLaunchKernelGGL(k_bow_triangulate_finish_batch, dim3(NL, 1, 1), dim3(256, 1, 1), 0, ts, (const TriParams*)dT);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = arena_download(ts);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(ts);
-        for (int k = 0; k < NL; k++) { orbhip_tri_pair& Q = pairs[live[k]]; for (int i = 0; i < n1; i++) Q.match12[i] = -1; }
-        return orbhip_set_error(ORBHIP_ERR_HIP, "search_for_triangulation_batch: %s", hipGetErrorString(e));
-    }
-    for (int k = 0; k < NL; k++) pairs[live[k]].nmatches = tail[k][ORBHIP_HISTO_LENGTH];
-    ORBHIP_RECORD(for (int k = 0; k < NL; k++) {               // one record per pair, the arrays of orbhip_search_for_triangulation in the same order
-        const orbhip_tri_pair& Q = pairs[live[k]]; const orbhip_tri_side &a = *kf1, &b = *Q.kf2;
-        TestRecord R(3); const float epi[2] = {Q.ex, Q.ey}; const int ipar[3] = {only_stereo, check_ori, Q.nmatches};
-        R.put(a.desc, (size_t)a.n * 32); R.put(a.kp, (size_t)a.n * 4); R.put(a.has_mp, a.n); R.put(a.stereo, a.n); R.put(a.fv_node, a.nfv); R.put(a.fv_off, (size_t)a.nfv + 1); R.put(a.fv_feat, a.fv_off[a.nfv]);
-        R.put(b.desc, (size_t)b.n * 32); R.put(b.kp, (size_t)b.n * 4); R.put(b.has_mp, b.n); R.put(b.stereo, b.n); R.put(b.fv_node, b.nfv); R.put(b.fv_off, (size_t)b.nfv + 1); R.put(b.fv_feat, b.fv_off[b.nfv]);
-        R.put(Q.F12, 9); R.put(epi, 2); R.put(b.scale_factors, b.nlevels); R.put(b.level_sigma2, b.nlevels); R.put(ipar, 3); R.put(Q.match12, a.n);
-    });
-    return ORBHIP_OK;
+    if (!match12 || !nmatches) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    const orbhip_tri_side s1 = {desc1, kp1, has_mp1, stereo1, n1, fv1_node, fv1_off, fv1_feat, nfv1, nullptr, nullptr, 0};
+    const orbhip_tri_side s2 = {desc2, kp2, has_mp2, stereo2, n2, fv2_node, fv2_off, fv2_feat, nfv2, F12 ? scale_factors2 : nullptr, level_sigma2_2, nlevels2};      // (no F12: refused like any other missing array of a pair with work)
+    orbhip_tri_pair Q = {&s2, {0.f}, ex, ey, match12, 0};
+    if (F12) memcpy(Q.F12, F12, sizeof Q.F12);
+    const orbhip_status st = search_for_triangulation_pairs("search_for_triangulation", device, &s1, 1, &Q, only_stereo, check_ori);
+    *nmatches = Q.nmatches;
+    return st;
 }

@@ -214,7 +214,6 @@ void orbhip_launch_match_candidates(const MatchParams& M, int nslots, hipStream_
 void orbhip_launch_match_select(const MatchParams& M, int nslots, hipStream_t s);
 
 // shared with orbhip_bow.hip
-void orbhip_bow_thread_release();
 // the BowVector orbhip_compute_bow left in HBM for `frame` of ctx's last call (orbhip_kfdb_query_frame reads it in place): ids, weights, the count, the arrays' capacity
 orbhip_status orbhip_bow_resident(orbhip_ctx* ctx, orbhip_voc* voc, int frame, const uint32_t** d_id, const double** d_val, const int** d_nbow, int* cap, int* device, int* nwords, hipStream_t* s);
 void orbhip_bow_forget_ctx(const orbhip_ctx* ctx);      // frees the per-context BoW workspaces every live vocabulary keeps for ctx (called by orbhip_destroy)
@@ -229,6 +228,21 @@ __device__ __forceinline__ int orbhip_writelane(int v, int dst_lane, int old)
     return (int)__lane_id() == dst_lane ? v : old;
 #endif
 }
+// One element of a read-only table at an index every lane agrees on, through the SCALAR cache (s_load: the result lands in SGPRs and counts on lgkmcnt).
+// As an ordinary load the compiler makes it a vector load - the kernel also stores to global memory, so it may not assume the table constant - and waiting
+// for a vector load means waiting for every LDS-DMA request issued before it (vmcnt returns in order).  Tables only: written by the host before the launch (orbhip_kernels_extract.hip's row tables, orbhip_bow.hip's parameter blocks).
+#ifdef __HIPCC__
+#define ORBHIP_CONSTANT __attribute__((address_space(4)))
+#else
+#define ORBHIP_CONSTANT                  // (the test emulation has one address space)
+#endif
+template <typename T> __device__ __forceinline__ const ORBHIP_CONSTANT T* scalar_ptr(const T* p)
+{
+    const unsigned long long a = (unsigned long long)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+    return (const ORBHIP_CONSTANT T*)(((unsigned long long)hi << 32) | lo);
+}
+template <typename T> __device__ __forceinline__ T scalar_load(const T* p) { return *scalar_ptr(p); }
 // ---- the calling thread's arena for the host-pointer ("stateless") matcher entry points: every array of a call is laid out in ONE device
 // allocation (grow-only, per thread) whose head mirrors a pinned host block, so that all inputs travel in one copy and all outputs in one copy
 #include <vector>

@@ -49,16 +49,6 @@ template <typename T> __device__ __forceinline__ ORBHIP_GLOBAL T* uniform_ptr(T*
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
     return (ORBHIP_GLOBAL T*)(((unsigned long long)hi << 32) | lo);
 }
-// One element of a read-only table at an index every lane agrees on, through the SCALAR cache (s_load: the result lands in SGPRs and counts on lgkmcnt).
-// As an ordinary load the compiler makes it a vector load - the kernel also stores to global memory, so it may not assume the table constant - and waiting
-// for a vector load means waiting for every LDS-DMA request issued before it (vmcnt returns in order).  Tables only: written by the host before the launch.
-#define ORBHIP_CONSTANT __attribute__((address_space(4)))
-template <typename T> __device__ __forceinline__ T scalar_load(const T* p)
-{
-    const unsigned long long a = (unsigned long long)p;
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
-    return *(const ORBHIP_CONSTANT T*)(((unsigned long long)hi << 32) | lo);
-}
 // LDS-DMA: every lane's dword goes from global memory straight to LDS dword (lane) of the 256-byte block at lds_block, without a
 // VGPR round trip (global_load_lds_dword; M0 = block address, wave-uniform).  The source may sit at any byte address
 // (tools/lds_dma_probe.hip, measured on MI355X).  The loads count on vmcnt: lds_dma_wait() before the first LDS read.

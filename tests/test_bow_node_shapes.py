@@ -16,8 +16,10 @@ Case -> branch:
   test_triangulation_node_shapes             k_bow_triangulate's two walks up to an 8193-feature node (no limit there), selective epipolar gate, the epipole's
                                              radius deciding planted pairs in both walks (the register walk's precomputed near-epipole flags too)
   test_fused_forms_at_the_line_gate          the fp_contract kernel against the model's fused statements where they and the unfused ones part
-  test_batch_forms                           k_bow_match_batch / k_bow_triangulate_batch: mixed shapes, an empty side, a shared side
+  test_batch_forms                           several pairs in one launch (the prefix table from block to pair): mixed shapes, an empty side, a shared side
   test_seeded_sweep_*                        random shapes, 1 .. 300 nodes: few large ones; over 256 on both sides (bisection by every workgroup of a full grid)
+Single-pair and batched entry points run the same kernels and the same host routine (a single-pair call is a batch of one), so every case here is on the code
+the back end's loops use; tests/test_bow_pair_contract.py pins the two forms to each other.
 For taken_hi and the cross-block `taken` the evidence is the "first claimant removed -> the second one's answer changes" assertion."""
 import ctypes as C
 import os

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Round 5's new kernels under the profiler (tools/gpu_pmc.sh <tag> <passes> r05): bag of words for one frame on an ORBvoc-shaped vocabulary (k_bow_descend,
-k_bow_assemble: 1000 and 2000 features), SearchByBoW / SearchForTriangulation on its 100-node partition (k_bow_match, k_bow_triangulate), stereo pairs as one call
+k_bow_assemble: 1000 and 2000 features), SearchByBoW / SearchForTriangulation on its 100-node partition (k_bow_match, k_bow_triangulate: each call a batch of one pair on the kernels the batched entries use), stereo pairs as one call
 (k_stereo_rows on 1024 threads), and two 2000-query scans of a 2 M-row descriptor database on the FP4 matrix path (k_hamming_nn_fp4)."""
 import os
 import sys

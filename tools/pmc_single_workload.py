@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The single-image kernels under the profiler (tools/gpu_pmc.sh <tag> <passes> single): what ORB_SLAM2 drives - 30 single-image extraction calls, 30 stereo pairs
 as one call each with a motion-model and a local-map search on the resident frame behind them (k_pyramid_cascade, k_fast_cells, k_blur_quadtree, k_describe,
-k_stereo_*, k_match_grid, k_proj_candidates / k_proj_select), and a few stateless back-end calls (k_best_in_window, k_bow_match, k_bow_triangulate)."""
+k_stereo_*, k_match_grid, k_proj_candidates / k_proj_select), and a few stateless back-end calls (k_best_in_window, k_bow_match, k_bow_triangulate - single-pair calls, run as
+batches of one by the kernels of the batched entries)."""
 import os
 import sys
 
