@@ -662,10 +662,10 @@ orbhip_status run_pipeline(orbhip_ctx* c, int nimg, const uint8_t* d_img0, long 
         M.kp2 = c->distorted ? c->d_out_kpun[cur] : c->d_out_kp[cur]; M.desc2 = c->d_out_desc[cur]; M.n2 = c->d_out_n[cur];
         M.lvl_stride = c->L; M.list1 = nullptr; M.prev_from_kp1 = 1;
         M.cap = c->out_cap; M.min_x = c->bounds.min_x; M.min_y = c->bounds.min_y; M.max_x = c->bounds.max_x; M.max_y = c->bounds.max_y;
-        M.grid_start = c->d_grid_start; M.grid_items = c->d_grid_items; M.grid_xy = c->d_grid_xy; M.cand = c->d_cand; M.top = c->d_top; M.ncand = c->d_ncand; M.cand_stride = c->lvl0_cap; M.lvl0_cap = c->lvl0_cap;
+        M.grid_start = c->d_grid_start; M.grid_items = c->d_grid_items; M.grid_xy = c->d_grid_xy; M.cand = c->d_cand; M.top = c->d_top; M.ncand = c->d_ncand; M.cand_stride = c->lvl0_cap; M.lvl0_cap = c->lvl0_cap; M.tab_cap = c->lvl0_cap;      // (level 0 of a frame holds at most lvl0_cap key points)
         M.prev = c->d_prev; M.matches12 = c->d_m12; M.nmatches = c->d_nm; M.window = window; M.nnratio = nnratio; M.check_ori = check_ori; M.slot0 = 0;
-        if (orbhip_match_select_big(c->out_cap, c->lvl0_cap)) {     // nfeatures beyond what LDS holds: the select kernel's tables in device memory, [slot][...], allocated at the first matched call
-            if (!c->d_match_ws) HIPCHK(dalloc(&c->d_match_ws, (size_t)c->B * orbhip_match_select_ints(c->out_cap, c->lvl0_cap)));
+        if (orbhip_match_select_big(c->lvl0_cap, c->lvl0_cap)) {     // level-0 key points beyond what LDS holds: the select kernel's tables in device memory, [slot][...], allocated at the first matched call
+            if (!c->d_match_ws) HIPCHK(dalloc(&c->d_match_ws, (size_t)c->B * orbhip_match_select_ints(c->lvl0_cap, c->lvl0_cap)));
             M.big_ws = c->d_match_ws;
         }
         // matcher of this batch on its own stream: latency-bound (one wave per slot), overlaps the next call's extraction

@@ -109,18 +109,19 @@ struct MatchParams {        // SearchForInitialization over camera slots (ORBmat
     int cap;                                      // keypoint capacity per frame (stride of the arrays above)
     float min_x, min_y, max_x, max_y;                                   // Frame::mnMinX .. mnMaxY (Frame.cc:436-464)
     int* grid_start; int* grid_items; float2* grid_xy;   // [slot][GRID_CELLS+1], [slot][cap], [slot][cap]  (Frame.cc:230-245 on F2, level 0 only)
-    unsigned* cand; int* ncand; int cand_stride;  // [slot][n1_lvl0_cap][cand_stride]: i2 | dist<<16, canonical order
+    unsigned* cand; int* ncand; int cand_stride;  // [slot][n1_lvl0_cap][cand_stride]: t | dist<<20 (t: position of the candidate in the slot's bucket table), canonical order
     unsigned* top;                                // [slot][n1_lvl0_cap][5]: records of the 4 best candidates of the whole list + "more" flag
     int lvl0_cap;
+    int tab_cap;                                  // entries of a slot's bucket table that the matcher addresses: at least F2's octave-0 key points (k_match_select's per-feature tables have this many entries)
     float* prev;                                  // [slot][cap][2] vbPrevMatched (in/out)
     int* matches12; int* nmatches;                // [slot][cap], [slot]
     int window; float nnratio; int check_ori;
     int slot0;                                    // first camera slot of this launch group
     int grid_all_levels;                          // 0: buckets hold level-0 keypoints only (SearchForInitialization); 1: all keypoints
-    int* big_ws;                                  // [slot][orbhip_match_select_ints(cap, lvl0_cap)] when k_match_select's tables do not fit LDS (orbhip_match_select_big); nullptr otherwise
+    int* big_ws;                                  // [slot][orbhip_match_select_ints(tab_cap, lvl0_cap)] when k_match_select's tables do not fit LDS (orbhip_match_select_big); nullptr otherwise
 };
-size_t orbhip_match_select_ints(int cap, int lvl0_cap);      // ints of k_match_select's per-slot tables
-bool orbhip_match_select_big(int cap, int lvl0_cap);         // they exceed the LDS budget: the caller provides MatchParams::big_ws
+size_t orbhip_match_select_ints(int tab_cap, int lvl0_cap);  // ints of k_match_select's per-slot tables
+bool orbhip_match_select_big(int tab_cap, int lvl0_cap);         // they exceed the LDS budget: the caller provides MatchParams::big_ws
 
 struct StereoSide {         // device-resident results + pyramid of one extractor context (its last call)
     const orbhip_keypoint* kp; const uint8_t* desc; const int* n;

@@ -7,11 +7,13 @@
 //   k_hamming_nn_fp4b                the same scan as +-1 FP4 products on the matrix cores (databases from 32 K rows on)
 //   k_match_grid                     Frame::AssignFeaturesToGrid (Frame.cc:230-245, 382-392): 64x48 buckets, keypoint order
 //   k_match_candidates               Frame::GetFeaturesInArea (Frame.cc:327-380) in canonical order + all Hamming distances,
-//                                    one wavefront per previous-frame keypoint; also records each key point's four best candidates
+//                                    a row of 16 lanes per previous-frame keypoint, four key points per wavefront; also records each
+//                                    key point's four best candidates.  A candidate is named by its position in the bucket table.
 //   k_match_select                   the order-dependent part of SearchForInitialization (ORBmatcher.cc:418-517): one
-//                                    wavefront per camera slot decides 64 key points per step from those records (a candidate is
-//                                    skipped once matched at a distance <= the query's), rescans the rare key point whose records
-//                                    are used up, then rotation histogram, ComputeThreeMaxima (:1601-1642), vbPrevMatched update.
+//                                    wavefront (= workgroup) per camera slot decides 64 key points per step from those records (a
+//                                    candidate is skipped once matched at a distance <= the query's), rescans the rare key point whose
+//                                    records are used up, then rotation histogram, ComputeThreeMaxima (:1601-1642), vbPrevMatched update.
+//                                    Per-feature tables by table position: 2 x level-0 key points of F2 + level-0 key points of F1 words.
 #include "orbhip_internal.h"
 #include <cstdlib>
 #include <cstring>
@@ -583,9 +585,9 @@ void orbhip_launch_match_grid(const MatchParams& M, int nslots, hipStream_t s)
 // index.  GetFeaturesInArea visits the cells [floor((x-r)/w) .. ceil((x+r)/w)] x [..] and keeps keypoints with |dx| < r and
 // |dy| < r (Frame.cc:327-380); a keypoint that passes the distance test always lies in a visited cell (its cell is
 // round(kx/w), and floor(a) <= round(v) <= ceil(b) for a < v < b; the sub-ulp slack of the float subtraction is far below
-// the 0.5 of the rounding), so the result is the sub-sequence of the whole table that passes the distance test.  One
-// wavefront scans the table (a few hundred entries: coalesced, all loads in flight at once) instead of walking ~300
-// mostly empty cells with dependent loads; ballot ranks keep the order.
+// the 0.5 of the rounding), so the result is the sub-sequence of the whole table that passes the distance test.  The
+// table is scanned (coalesced, several loads in flight at once) instead of walking ~300 mostly empty cells with dependent
+// loads; ballot ranks keep the order.
 // wave64 minimum with DPP row shifts / broadcasts (6 dependent 4-cycle VALU steps); result broadcast from lane 63
 __device__ __forceinline__ int wave_min_dpp(int v)
 {
@@ -601,15 +603,30 @@ __device__ __forceinline__ int wave_min_dpp(int v)
 #define MS_K 4                          // best candidates recorded per query (under the initial state: nothing matched yet)
 #define MS_REC (MS_K + 1)               // + one word: more candidates exist
 #define MS_NONE 0xFFFFFFFFu
-#define MC_CHUNKS 8
+#define MC_CHUNKS 4
+#define MC_KPW 4                        // key points per wavefront: one per DPP row of 16 lanes
+// minimum over the 16 lanes of a DPP row, in every lane of the row (4 dependent VALU steps; every row of the wave on its own)
+__device__ __forceinline__ int row_min_dpp(int v)
+{
+    v = min(v, __builtin_amdgcn_update_dpp(IMAX, v, 0xB1, 0xf, 0xf, false));       // quad_perm:[1,0,3,2]
+    v = min(v, __builtin_amdgcn_update_dpp(IMAX, v, 0x4E, 0xf, 0xf, false));       // quad_perm:[2,3,0,1] -> quad minimum
+    v = min(v, __builtin_amdgcn_update_dpp(IMAX, v, 0x141, 0xf, 0xf, false));      // row_half_mirror -> minimum of 8
+    v = min(v, __builtin_amdgcn_update_dpp(IMAX, v, 0x128, 0xf, 0xf, false));      // row_ror:8 -> row minimum
+    return v;
+}
+// A wavefront takes four consecutive level-0 key points of F1, one per row of 16 lanes: the run of a key point is about two 64-entry passes long, and a
+// whole wave per key point spent most of its instructions on per-wave overhead (load guards of eight chunks, the six-step wave minimum four times
+// over, the setup chain).  A row walks its own run 16 entries at a time, in table order; rows are masked individually and the loop ends when
+// every row is done.  Nothing else changes: list positions `pos`, the clamp at cand_stride, the records.
 __global__ __launch_bounds__(256) void k_match_candidates(MatchParams M, float gwInv, float ghInv)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, slot = blockIdx.y + M.slot0;
-    const int j1 = blockIdx.x * 4 + wave;
-    const int n1l = M.n1_lvl0[slot * M.lvl_stride];
-    if (j1 >= n1l || j1 >= M.lvl0_cap) return;
+    const int row = lane >> 4, rl = lane & 15;
+    const int n1l = min(M.n1_lvl0[slot * M.lvl_stride], M.lvl0_cap);
+    if ((blockIdx.x * 4 + wave) * MC_KPW >= n1l) return;                       // (the whole wave)
+    const bool live = (blockIdx.x * 4 + wave) * MC_KPW + row < n1l;            // a ragged last wave: its idle rows go along with an empty run
+    const int j1 = live ? (blockIdx.x * 4 + wave) * MC_KPW + row : n1l - 1;
     const int i1 = M.list1 ? M.list1[(long long)slot * M.lvl0_cap + j1] : j1;   // level-major extractor output: level 0 = indices [0, n_lvl0)
-    const int nitems = M.grid_start[(long long)slot * (ORBHIP_GRID_CELLS + 1) + ORBHIP_GRID_CELLS];
     const int* gitems = M.grid_items + (long long)slot * M.cap;
     const float2* gxy = M.grid_xy + (long long)slot * M.cap;
     unsigned* cand = M.cand + ((long long)slot * M.lvl0_cap + j1) * M.cand_stride;
@@ -619,7 +636,7 @@ __global__ __launch_bounds__(256) void k_match_candidates(MatchParams M, float g
     const float r = (float)M.window;
     const unsigned long long* d1 = (const unsigned long long*)(M.desc1 + ((long long)slot * M.cap + i1) * 32);
     const unsigned long long q0 = d1[0], q1 = d1[1], q2 = d1[2], q3 = d1[3];
-    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned below = (1u << rl) - 1u;
     int nc = 0;
     int tk[MS_K]; unsigned te[MS_K]; int nsel = 0;          // this lane's MS_K smallest (distance, list position) keys + their records
 #pragma unroll
@@ -627,219 +644,228 @@ __global__ __launch_bounds__(256) void k_match_candidates(MatchParams M, float g
     // The table is ordered by grid column first, so the entries of the columns the window can reach are ONE contiguous run of it: the columns
     // GetFeaturesInArea visits (Frame.cc:333-343: floor((x - mnMinX - r) inv) .. ceil((x - mnMinX + r) inv)), widened by one on either side (far
     // more than the float slack of that arithmetic).  A key point outside the run fails |dx| < r, so scanning the run alone gives the same
-    // sub-sequence as scanning the whole table: at the metric's window (100 px of 1241) that is a fifth of it, 2 passes of 64 entries instead of 7.
+    // sub-sequence as scanning the whole table: at the metric's window (100 px of 1241) that is a fifth of it.
     const int* gstart = M.grid_start + (long long)slot * (ORBHIP_GRID_CELLS + 1);
     const float cl = __fmul_rn(__fsub_rn(__fsub_rn(x, M.min_x), r), gwInv), ch = __fmul_rn(__fadd_rn(__fsub_rn(x, M.min_x), r), gwInv);
     // (the comparisons are written so that a NaN position scans the whole table, like the distance test it would fail everywhere)
     const int col_lo = cl >= 1.0f ? (int)fminf(floorf(cl) - 1.0f, (float)ORBHIP_GRID_COLS) : 0;
     const int col_hi = ch < (float)(ORBHIP_GRID_COLS - 2) ? (int)fmaxf(ceilf(ch) + 2.0f, 0.0f) : ORBHIP_GRID_COLS;       // one past the last column scanned
-    const int t_lo = __builtin_amdgcn_readfirstlane(gstart[min(col_lo, col_hi) * ORBHIP_GRID_ROWS]), t_hi = __builtin_amdgcn_readfirstlane(gstart[col_hi * ORBHIP_GRID_ROWS]);
-    (void)nitems;
-    for (int tb = t_lo; tb < t_hi; tb += 64 * MC_CHUNKS) {
+    // (tab_cap: what k_match_select's tables hold - the callers size it by F2's level-0 key points, which is all the table can list)
+    const int t_lo = min(gstart[min(col_lo, col_hi) * ORBHIP_GRID_ROWS], M.tab_cap), t_hi = live ? min(gstart[col_hi * ORBHIP_GRID_ROWS], M.tab_cap) : 0;
+    for (int tb = t_lo + rl; __ballot(tb - rl < t_hi) != 0ull; tb += 16 * MC_CHUNKS) {
         float2 k[MC_CHUNKS]; int it[MC_CHUNKS];
 #pragma unroll
         for (int c = 0; c < MC_CHUNKS; c++) {
-            const int t = tb + 64 * c + lane;
+            const int t = tb + 16 * c;
             k[c].x = 0.0f; k[c].y = 0.0f; it[c] = 0;
             if (t < t_hi) { k[c] = gxy[t]; it[c] = gitems[t]; }
         }
 #pragma unroll
         for (int c = 0; c < MC_CHUNKS; c++) {
-            if (tb + 64 * c >= t_hi) break;
-            const bool ok = tb + 64 * c + lane < t_hi && fabsf(__fsub_rn(k[c].x, x)) < r && fabsf(__fsub_rn(k[c].y, y)) < r;    // Frame.cc:367-371
+            const int t = tb + 16 * c;
+            const bool ok = t < t_hi && fabsf(__fsub_rn(k[c].x, x)) < r && fabsf(__fsub_rn(k[c].y, y)) < r;    // Frame.cc:367-371
             const unsigned long long m = __ballot(ok);
             if (m == 0) continue;
-            const int pos = nc + __popcll(m & below);
+            const unsigned mr = (unsigned)(m >> (16 * row)) & 0xFFFFu;          // this row's lanes
+            const int pos = nc + __popc(mr & below);
             if (ok && pos < M.cand_stride) {
                 const unsigned long long* d2 = (const unsigned long long*)(M.desc2 + ((long long)slot * M.cap + it[c]) * 32);
                 const int dist = __popcll(q0 ^ d2[0]) + __popcll(q1 ^ d2[1]) + __popcll(q2 ^ d2[2]) + __popcll(q3 ^ d2[3]);
-                unsigned rec = (unsigned)it[c] | ((unsigned)dist << 20);       // DescriptorDistance (ORBmatcher.cc:442)
+                unsigned rec = (unsigned)t | ((unsigned)dist << 20);       // table position | DescriptorDistance (ORBmatcher.cc:442)
                 cand[pos] = rec;
                 int key = (dist << 20) | pos;
                 nsel++;
 #pragma unroll
                 for (int k = 0; k < MS_K; k++) if (key < tk[k]) { const int tkk = tk[k]; const unsigned tee = te[k]; tk[k] = key; te[k] = rec; key = tkk; rec = tee; }   // sorted insert
             }
-            nc += __popcll(m);
+            nc += __popc(mr);
         }
     }
     nc = min(nc, M.cand_stride);
-    if (lane == 0) M.ncand[(long long)slot * M.lvl0_cap + j1] = nc;
+    if (live && rl == 0) M.ncand[(long long)slot * M.lvl0_cap + j1] = nc;
     // The best / second-best update of the reference (ORBmatcher.cc:447-456) ends with the two smallest (distance, list position)
     // keys among the candidates it does not skip.  Record the MS_K smallest of the whole list: k_match_select takes the first two
-    // that are not skipped at its turn.
-    unsigned out = MS_NONE; int popped = 0;
+    // that are not skipped at its turn.  Keys hold the list position, so a row's minimum lives in exactly one of its lanes: that lane writes
+    // its record and drops it.
+    unsigned* top = M.top + ((long long)slot * M.lvl0_cap + j1) * MS_REC;
+    int popped = 0, nrec = 0;
 #pragma unroll
     for (int r = 0; r < MS_K; r++) {
-        const int m = wave_min_dpp(tk[0]);
-        if (m == IMAX) break;
-        const int owner = __ffsll((long long)__ballot(tk[0] == m)) - 1;
-        const unsigned rec = (unsigned)__builtin_amdgcn_readlane((int)te[0], owner);
-        if (lane == r) out = rec;
-        if (lane == owner) {
+        const int m = row_min_dpp(tk[0]);
+        if (m != IMAX) nrec = r + 1;
+        if (m != IMAX && tk[0] == m) {
+            if (live) top[r] = te[0];
             popped++;
 #pragma unroll
             for (int k = 0; k + 1 < MS_K; k++) { tk[k] = tk[k + 1]; te[k] = te[k + 1]; }
             tk[MS_K - 1] = IMAX; te[MS_K - 1] = MS_NONE;
         }
     }
-    const bool more = __ballot(nsel > popped) != 0ull;
-    unsigned* top = M.top + ((long long)slot * M.lvl0_cap + j1) * MS_REC;
-    if (lane < MS_K) top[lane] = out;
-    if (lane == MS_K) top[MS_K] = more ? 1u : 0u;
+    const bool more = ((unsigned)(__ballot(nsel > popped) >> (16 * row)) & 0xFFFFu) != 0u;
+    if (live && rl >= nrec && rl < MS_K) top[rl] = MS_NONE;
+    if (live && rl == MS_K) top[MS_K] = more ? 1u : 0u;
 }
 
 void orbhip_launch_match_candidates(const MatchParams& M, int nslots, hipStream_t s)
 {
     const float gwInv = (float)ORBHIP_GRID_COLS / (float)(M.max_x - M.min_x), ghInv = (float)ORBHIP_GRID_ROWS / (float)(M.max_y - M.min_y);
-    hipLaunchKernelGGL(k_match_candidates, dim3((M.lvl0_cap + 3) / 4, nslots, 1), dim3(256, 1, 1), 0, s, M, gwInv, ghInv);
+    hipLaunchKernelGGL(k_match_candidates, dim3((M.lvl0_cap + 4 * MC_KPW - 1) / (4 * MC_KPW), nslots, 1), dim3(256, 1, 1), 0, s, M, gwInv, ghInv);
 }
 
 // ------------------------------------------------------------------------------------------------ select
 
-#define MS_T 256
+#define MS_T 64
 
-// One workgroup per camera slot.  All 4 waves initialise the per-slot tables in LDS, then wave 0 alone resolves the
-// order-dependent loop over F1's level-0 keypoints, 64 of them per step, from the MS_K records k_match_candidates left per key
-// point (see the loop).  The candidate lists themselves (i2 | dist<<20, canonical order) stay in HBM/L2 and are only read for the
-// rare key point whose records are used up; the kernel's LDS footprint stays small enough not to displace the workgroups of
-// the extraction kernels it runs beside (an 80 KB staged copy of the lists used to halve k_fast_cells' occupancy on every CU).
-__device__ __forceinline__ int orbhip_match_select_ints_d(int cap, int lvl0_cap) { return 4 * cap + 4 * lvl0_cap + ORBHIP_HISTO_LENGTH + 8; }
-// BIG: the per-slot tables in device memory (M.big_ws) instead of LDS, for frames of more key points than the LDS holds (nfeatures from ~8300 on at 1080p; the
-// reference takes any nFeatures, Tracking.cc:113-125).  Same statements on volatile global words (one wave resolves the loop: program order is the order), see
-// proj_select_body<BIG>.
+// One wavefront (a 64-thread workgroup) per camera slot: it initialises the slot's tables and then resolves the order-dependent loop over F1's
+// level-0 keypoints, 64 of them per step, from the MS_K records k_match_candidates left per key point (see the loop).
+//
+// A feature of F2 is named by its POSITION t in the slot's bucket table (k_match_grid), not by its key point index: only the table's entries
+// (octave-0 key points inside the grid) can ever be candidates, so the per-feature state has tab_cap entries, not cap, whatever the order of F2's
+// key points; results are mapped back through grid_items / grid_xy where they are written.  Per slot:
+//   s_mdm[t]    vMatchedDistance[i2] << 21 | (vnMatches21[i2] + 1)      written together on every accept; distance MS_MD_NONE = nothing matched yet
+//   s_stamp[t]  lowest undecided query that wants to claim feature t
+//   s_acc[j1]   ((t + 1) << 6) | alive << 5 | rotation bin              the feature query j1 accepted (a query decides once); alive = not stolen since
+//   s_hist      rotation histogram + the three maxima
+// 2 tab_cap + lvl0_cap + 38 words: 5.4 KB at 2000 features on 1241x376, so the workgroup fits beside the extraction kernels it runs next to (k_fast_cells
+// fills a CU's LDS exactly; tables of cap entries - 40 KB - displaced two or three of its workgroups per slot, profiles/matcher_beside_extraction.txt).
+// The angles are not staged: rotHist only counts (ORBmatcher.cc:470-480 pushes, nothing pops when a match is stolen), so the bin of every accepted
+// pair is computed after the loop, all queries in parallel, from the key point records in memory.  The candidate lists (t | dist<<20, canonical
+// order) and their counts stay in HBM/L2 and are only read for the rare key point whose records are used up.
+#define MS_MD_NONE 0x3FF
+#define MS_J_MASK 0x1FFFFF
+__device__ __forceinline__ int orbhip_match_select_ints_d(int tab_cap, int lvl0_cap) { return 2 * tab_cap + lvl0_cap + ORBHIP_HISTO_LENGTH + 8; }
+// BIG: the per-slot tables in device memory (M.big_ws) instead of LDS, for frames of more level-0 key points than the LDS holds (the reference takes any
+// nFeatures, Tracking.cc:113-125).  Same statements on volatile global words (one wave resolves the loop: program order is the order), see proj_select_body<BIG>.
 template <bool BIG> __device__ __forceinline__ void match_select_body(const MatchParams& M)
 {
     typedef typename std::conditional<BIG, volatile int, int>::type TI;
-    typedef typename std::conditional<BIG, volatile float, float>::type TF;
-    const int slot = blockIdx.x + M.slot0, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n1 = M.n1[slot], n2 = M.n2[slot];
+    const int slot = blockIdx.x + M.slot0, lane = threadIdx.x;
+    const int n1 = M.n1[slot];
     const int n1l = min(M.n1_lvl0[slot * M.lvl_stride], M.lvl0_cap);
     const int* list1 = M.list1 ? M.list1 + (long long)slot * M.lvl0_cap : nullptr;
+    const int nt = min(M.grid_start[(long long)slot * (ORBHIP_GRID_CELLS + 1) + ORBHIP_GRID_CELLS], M.tab_cap);
     HIP_DYNAMIC_SHARED(int, lds)
-    TI* s_md = BIG ? M.big_ws + (long long)(blockIdx.x + M.slot0) * (long long)orbhip_match_select_ints_d(M.cap, M.lvl0_cap) : lds;     // vMatchedDistance[i2]
-    TI* s_m21 = s_md + M.cap;               // vnMatches21[i2]
-    TI* s_m12 = s_m21 + M.cap;              // vnMatches12[i1] for level-0 i1
-    TI* s_bin = s_m12 + M.lvl0_cap;         // rotation bin of the accepted match of i1, -1 = none
-    TI* s_nc = s_bin + M.lvl0_cap;          // candidate count per level-0 i1
-    TI* s_hist = s_nc + M.lvl0_cap;         // [HISTO_LENGTH] + misc
-    TI* s_stamp = s_hist + ORBHIP_HISTO_LENGTH + 8;                                // lowest undecided query that wants to claim feature i2
-    TF* s_ang1 = reinterpret_cast<TF*>(s_stamp + M.cap);                           // angle of F1's level-0 keypoint j1
-    TF* s_ang2 = s_ang1 + M.lvl0_cap;                                              // angle of F2's keypoint i2
+    TI* s_mdm = BIG ? M.big_ws + (long long)slot * (long long)orbhip_match_select_ints_d(M.tab_cap, M.lvl0_cap) : lds;
+    TI* s_stamp = s_mdm + M.tab_cap;
+    TI* s_acc = s_stamp + M.tab_cap;
+    TI* s_hist = s_acc + M.lvl0_cap;        // [HISTO_LENGTH] + misc
     auto amin = [](TI* p, int v) { atomicMin(const_cast<int*>(p), v); };
     auto aadd = [](TI* p, int v) { atomicAdd(const_cast<int*>(p), v); };
     const orbhip_keypoint* kp1 = M.kp1 + (long long)slot * M.cap;
     const orbhip_keypoint* kp2 = M.kp2 + (long long)slot * M.cap;
+    const int* gitems = M.grid_items + (long long)slot * M.cap;
+    const float2* gxy = M.grid_xy + (long long)slot * M.cap;
+    const int* ncand = M.ncand + (long long)slot * M.lvl0_cap;
     int* m12 = M.matches12 + (long long)slot * M.cap;
     float* prev = M.prev + (long long)slot * M.cap * 2;
     const unsigned* cand0 = M.cand + (long long)slot * M.lvl0_cap * M.cand_stride;
-    for (int i = tid; i < n2; i += MS_T) { s_md[i] = IMAX; s_m21[i] = -1; s_stamp[i] = IMAX; s_ang2[i] = kp2[i].angle; }
-    for (int i = tid; i < n1l; i += MS_T) { s_m12[i] = -1; s_bin[i] = -1; s_nc[i] = M.ncand[(long long)slot * M.lvl0_cap + i]; s_ang1[i] = kp1[list1 ? list1[i] : i].angle; }
-    for (int i = tid; i < ORBHIP_HISTO_LENGTH + 8; i += MS_T) s_hist[i] = 0;
-    for (int i = tid; i < n1; i += MS_T) { m12[i] = -1; if (M.prev_from_kp1) { prev[2 * i] = kp1[i].x; prev[2 * i + 1] = kp1[i].y; } }
+    const unsigned* top0 = M.top + (long long)slot * M.lvl0_cap * MS_REC;
+    for (int t = lane; t < nt; t += MS_T) { s_mdm[t] = MS_MD_NONE << 21; s_stamp[t] = IMAX; }
+    for (int i = lane; i < n1l; i += MS_T) s_acc[i] = 0;
+    for (int i = lane; i < ORBHIP_HISTO_LENGTH + 8; i += MS_T) s_hist[i] = 0;
+    for (int i = lane; i < n1; i += MS_T) { m12[i] = -1; if (M.prev_from_kp1) { prev[2 * i] = kp1[i].x; prev[2 * i + 1] = kp1[i].y; } }
     __syncthreads();
-    if (wave == 0) {
-        const float factor = 1.0f / ORBHIP_HISTO_LENGTH;
-        const unsigned* top0 = M.top + (long long)slot * M.lvl0_cap * MS_REC;
-        auto rot_bin = [&](int j1, int i2) -> int {                                        // :470-480
-            float rot = __fsub_rn(s_ang1[j1], s_ang2[i2]);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, factor));
-            if (bin == ORBHIP_HISTO_LENGTH) bin = 0;
-            return min(max(bin, 0), ORBHIP_HISTO_LENGTH - 1);
-        };
-        // 64 previous-frame key points per step.  A candidate is skipped once it is matched at a distance <= this query's
-        // (vMatchedDistance only ever decreases), so a query's best / second-best are the first two recorded candidates that are
-        // not skipped when its turn comes.  All lanes decide at once; a lane one of whose relevant records an earlier, still
-        // undecided lane wants to claim (atomicMin stamp) waits for the next iteration; only a query whose records are used up
-        // while its list holds more is rescanned from the list.
-        for (int jb = 0; jb < n1l; jb += 64) {
-            const int j1 = jb + lane;
-            const bool inb = j1 < n1l;
-            int ei[MS_K], ed[MS_K]; int nk = 0;
+    auto matched_dist = [&](int t) -> int { return s_mdm[t] >> 21; };                          // vMatchedDistance
+    auto accept_match = [&](int j1, int t, int dist) {                                          // :463-467
+        const int old = (s_mdm[t] & MS_J_MASK) - 1;
+        if (old >= 0) s_acc[old] = s_acc[old] & ~32;
+        s_acc[j1] = ((t + 1) << 6) | 32; s_mdm[t] = (dist << 21) | (j1 + 1);
+    };
+    // 64 previous-frame key points per step.  A candidate is skipped once it is matched at a distance <= this query's
+    // (vMatchedDistance only ever decreases), so a query's best / second-best are the first two recorded candidates that are
+    // not skipped when its turn comes.  All lanes decide at once; a lane one of whose relevant records an earlier, still
+    // undecided lane wants to claim (atomicMin stamp) waits for the next iteration; only a query whose records are used up
+    // while its list holds more is rescanned from the list.
+    for (int jb = 0; jb < n1l; jb += 64) {
+        const int j1 = jb + lane;
+        const bool inb = j1 < n1l;
+        int ei[MS_K], ed[MS_K]; int nk = 0;
+        const bool any = inb && ncand[j1] != 0;
 #pragma unroll
-            for (int k = 0; k < MS_K; k++) {
-                const unsigned t = (inb && s_nc[j1] != 0) ? top0[(long long)j1 * MS_REC + k] : MS_NONE;
-                ei[k] = (int)(t & 0xFFFFFu); ed[k] = (int)((t >> 20) & 0x1FFu);
-                if (t != MS_NONE) nk = k + 1;
+        for (int k = 0; k < MS_K; k++) {
+            const unsigned t = any ? top0[(long long)j1 * MS_REC + k] : MS_NONE;
+            ei[k] = (int)(t & 0xFFFFFu); ed[k] = (int)((t >> 20) & 0x1FFu);
+            if (t != MS_NONE) nk = k + 1;
+        }
+        const bool more = nk > 0 && top0[(long long)j1 * MS_REC + MS_K] != 0u;
+        int stamped = -1;
+        unsigned long long todo = __ballot(nk > 0);
+        while (todo) {
+            const bool mine = (todo >> lane) & 1ull;
+            const int lowest = __ffsll((long long)todo) - 1;
+            int a = -1, b = -1;
+#pragma unroll
+            for (int k = 0; k < MS_K; k++)
+                if (mine && k < nk && b < 0 && !(matched_dist(ei[k]) <= ed[k])) { if (a < 0) a = k; else b = k; }      // :444-445
+            const int ia = a >= 0 ? ei[a] : 0, da = a >= 0 ? ed[a] : IMAX, db = b >= 0 ? ed[b] : IMAX;
+            const bool exhausted = mine && more && b < 0;
+            const bool accept = mine && !exhausted && a >= 0 && da <= ORBHIP_TH_LOW && (float)da < __fmul_rn((float)db, M.nnratio);    // :459-461
+            const int want = accept ? ia : -1;
+            if (stamped >= 0 && stamped != want && s_stamp[stamped] == j1) s_stamp[stamped] = IMAX;       // withdraw an outdated claim
+            __builtin_amdgcn_wave_barrier();
+            if (want >= 0) amin(&s_stamp[want], j1);
+            stamped = want;
+            __builtin_amdgcn_wave_barrier();
+            bool unsure = false;
+            const int last = b >= 0 ? b : nk - 1;
+#pragma unroll
+            for (int k = 0; k < MS_K; k++)
+                if (mine && lane != lowest && k <= last && !(matched_dist(ei[k]) <= ed[k]) && s_stamp[ei[k]] < j1) unsure = true;
+            const unsigned long long bad = __ballot(unsure || exhausted);
+            const int first_bad = bad ? __ffsll((long long)bad) - 1 : 64;
+            const unsigned long long commit = first_bad == 64 ? todo : (todo & ((1ull << first_bad) - 1ull));
+            const bool win = ((commit >> lane) & 1ull) && accept;
+            if (win) {                                                                  // claimed features are distinct within one commit
+                accept_match(j1, ia, da);
+                if (s_stamp[ia] == j1) s_stamp[ia] = IMAX;                              // a decided claim lives in vMatchedDistance
+                stamped = -1;
             }
-            const bool more = nk > 0 && top0[(long long)j1 * MS_REC + MS_K] != 0u;
-            int stamped = -1;
-            unsigned long long todo = __ballot(nk > 0);
-            while (todo) {
-                const bool mine = (todo >> lane) & 1ull;
-                const int lowest = __ffsll((long long)todo) - 1;
-                int a = -1, b = -1;
-#pragma unroll
-                for (int k = 0; k < MS_K; k++)
-                    if (mine && k < nk && b < 0 && !(s_md[ei[k]] <= ed[k])) { if (a < 0) a = k; else b = k; }      // :444-445
-                const int ia = a >= 0 ? ei[a] : 0, da = a >= 0 ? ed[a] : IMAX, db = b >= 0 ? ed[b] : IMAX;
-                const bool exhausted = mine && more && b < 0;
-                const bool accept = mine && !exhausted && a >= 0 && da <= ORBHIP_TH_LOW && (float)da < __fmul_rn((float)db, M.nnratio);    // :459-461
-                const int want = accept ? ia : -1;
-                if (stamped >= 0 && stamped != want && s_stamp[stamped] == j1) s_stamp[stamped] = IMAX;       // withdraw an outdated claim
-                __builtin_amdgcn_wave_barrier();
-                if (want >= 0) amin(&s_stamp[want], j1);
-                stamped = want;
-                __builtin_amdgcn_wave_barrier();
-                bool unsure = false;
-                const int last = b >= 0 ? b : nk - 1;
-#pragma unroll
-                for (int k = 0; k < MS_K; k++)
-                    if (mine && lane != lowest && k <= last && !(s_md[ei[k]] <= ed[k]) && s_stamp[ei[k]] < j1) unsure = true;
-                const unsigned long long bad = __ballot(unsure || exhausted);
-                const int first_bad = bad ? __ffsll((long long)bad) - 1 : 64;
-                const unsigned long long commit = first_bad == 64 ? todo : (todo & ((1ull << first_bad) - 1ull));
-                const bool win = ((commit >> lane) & 1ull) && accept;
-                if (win) {                                                                  // claimed features are distinct within one commit
-                    const int old = s_m21[ia];
-                    if (old >= 0) s_m12[old] = -1;                                          // :463-467
-                    s_m12[j1] = ia; s_m21[ia] = j1; s_md[ia] = da;
-                    if (s_stamp[ia] == j1) s_stamp[ia] = IMAX;                              // a decided claim lives in vMatchedDistance
-                    stamped = -1;
-                    if (M.check_ori) { const int bin = rot_bin(j1, ia); s_bin[j1] = bin; aadd(&s_hist[bin], 1); }      // rotHist[bin].push_back(i1): never removed when stolen
-                }
-                __builtin_amdgcn_wave_barrier();
-                todo &= ~commit;
-                if (first_bad == 64) break;
-                if (first_bad != lowest || !((__ballot(exhausted) >> first_bad) & 1ull)) continue;
-                // rescan the list of key point jb + first_bad against the current state
-                todo &= ~(1ull << first_bad);
-                if (lane == first_bad && stamped >= 0 && s_stamp[stamped] == j1) s_stamp[stamped] = IMAX;
-                const int js = jb + first_bad, nc = s_nc[js];
-                const unsigned* cand = cand0 + (long long)js * M.cand_stride;
-                int best = IMAX, second = IMAX, bidx = -1;
-                for (int cb = 0; cb < nc; cb += 64) {
-                    const int t = cb + lane;
-                    const unsigned e = t < nc ? cand[t] : 0u;
-                    const int i2 = (int)(e & 0xFFFFFu), dist = (int)(e >> 20);
-                    const bool valid = t < nc && !(s_md[i2] <= dist);                    // :444-445
-                    // smallest (distance, lane) key by a DPP min network: strict '<' means the first candidate with the minimum
-                    // wins (:447-452); the runner-up is the minimum with that lane masked out
-                    const int key = valid ? ((dist << 6) | lane) : IMAX;
-                    const int k1 = wave_min_dpp(key);
-                    if (k1 == IMAX) continue;
-                    const int first = k1 & 63, wmin = k1 >> 6, ci = __builtin_amdgcn_readlane(i2, first);
-                    const int k2 = wave_min_dpp(lane == first ? IMAX : key);
-                    const int wsec = k2 == IMAX ? IMAX : (k2 >> 6);
-                    if (wmin < best) { second = min(best, wsec); best = wmin; bidx = ci; } else second = min(second, wmin);
-                }
-                if (best <= ORBHIP_TH_LOW && (float)best < __fmul_rn((float)second, M.nnratio)) {      // :459-461
-                    if (lane == 0) {
-                        const int old = s_m21[bidx];
-                        if (old >= 0) s_m12[old] = -1;
-                        s_m12[js] = bidx; s_m21[bidx] = js; s_md[bidx] = best;
-                        if (M.check_ori) { const int bin = rot_bin(js, bidx); s_bin[js] = bin; s_hist[bin] = s_hist[bin] + 1; }
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();                     // lane 0's LDS updates are read by the whole wave next
+            __builtin_amdgcn_wave_barrier();
+            todo &= ~commit;
+            if (first_bad == 64) break;
+            if (first_bad != lowest || !((__ballot(exhausted) >> first_bad) & 1ull)) continue;
+            // rescan the list of key point jb + first_bad against the current state
+            todo &= ~(1ull << first_bad);
+            if (lane == first_bad && stamped >= 0 && s_stamp[stamped] == j1) s_stamp[stamped] = IMAX;
+            const int js = jb + first_bad, nc = ncand[js];
+            const unsigned* cand = cand0 + (long long)js * M.cand_stride;
+            int best = IMAX, second = IMAX, bidx = -1;
+            for (int cb = 0; cb < nc; cb += 64) {
+                const int c = cb + lane;
+                const unsigned e = c < nc ? cand[c] : 0u;
+                const int t = (int)(e & 0xFFFFFu), dist = (int)(e >> 20);
+                const bool valid = c < nc && !(matched_dist(t) <= dist);              // :444-445
+                // smallest (distance, lane) key by a DPP min network: strict '<' means the first candidate with the minimum
+                // wins (:447-452); the runner-up is the minimum with that lane masked out
+                const int key = valid ? ((dist << 6) | lane) : IMAX;
+                const int k1 = wave_min_dpp(key);
+                if (k1 == IMAX) continue;
+                const int first = k1 & 63, wmin = k1 >> 6, ci = __builtin_amdgcn_readlane(t, first);
+                const int k2 = wave_min_dpp(lane == first ? IMAX : key);
+                const int wsec = k2 == IMAX ? IMAX : (k2 >> 6);
+                if (wmin < best) { second = min(best, wsec); best = wmin; bidx = ci; } else second = min(second, wmin);
             }
+            if (best <= ORBHIP_TH_LOW && (float)best < __fmul_rn((float)second, M.nnratio)) {      // :459-461
+                if (lane == 0) accept_match(js, bidx, best);
+            }
+            __builtin_amdgcn_wave_barrier();                     // lane 0's updates are read by the whole wave next
         }
     }
-    if (wave != 0) return;
     __builtin_amdgcn_wave_barrier();
     // nmatches of the reference (++ on accept, -- on steal :463-467 and on rotation reject :504-508) == final count of set entries
     if (M.check_ori) {
+        const float factor = 1.0f / ORBHIP_HISTO_LENGTH;
+        for (int j = lane; j < n1l; j += 64) {                    // rotHist[bin].push_back(i1) of every accept (:470-480), stolen later or not
+            const int w = s_acc[j];
+            if (w == 0) continue;
+            float rot = __fsub_rn(kp1[list1 ? list1[j] : j].angle, kp2[gitems[(w >> 6) - 1]].angle);
+            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+            int bin = (int)roundf(__fmul_rn(rot, factor));
+            if (bin == ORBHIP_HISTO_LENGTH) bin = 0;
+            bin = min(max(bin, 0), ORBHIP_HISTO_LENGTH - 1);
+            s_acc[j] = w | bin; aadd(&s_hist[bin], 1);
+        }
+        __builtin_amdgcn_wave_barrier();
         if (lane == 0) {                                          // ComputeThreeMaxima (:1601-1642)
             int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
             for (int i = 0; i < ORBHIP_HISTO_LENGTH; i++) {
@@ -853,14 +879,15 @@ template <bool BIG> __device__ __forceinline__ void match_select_body(const Matc
             s_hist[ORBHIP_HISTO_LENGTH] = ind1; s_hist[ORBHIP_HISTO_LENGTH + 1] = ind2; s_hist[ORBHIP_HISTO_LENGTH + 2] = ind3;
         }
         __builtin_amdgcn_wave_barrier();
-        const int ind1 = s_hist[ORBHIP_HISTO_LENGTH], ind2 = s_hist[ORBHIP_HISTO_LENGTH + 1], ind3 = s_hist[ORBHIP_HISTO_LENGTH + 2];
-        for (int j = lane; j < n1l; j += 64) { const int b = s_bin[j]; if (b >= 0 && b != ind1 && b != ind2 && b != ind3) s_m12[j] = -1; }
-        __builtin_amdgcn_wave_barrier();
     }
+    const int ind1 = s_hist[ORBHIP_HISTO_LENGTH], ind2 = s_hist[ORBHIP_HISTO_LENGTH + 1], ind3 = s_hist[ORBHIP_HISTO_LENGTH + 2];
     int cnt = 0;
     for (int j = lane; j < n1l; j += 64) {
-        const int m = s_m12[j];
-        if (m >= 0) { const int i1 = list1 ? list1[j] : j; cnt++; m12[i1] = m; prev[2 * i1] = kp2[m].x; prev[2 * i1 + 1] = kp2[m].y; }      // :515-517
+        const int w = s_acc[j], b = w & 31;
+        if (!(w & 32) || (M.check_ori && b != ind1 && b != ind2 && b != ind3)) continue;
+        const int t = (w >> 6) - 1, i1 = list1 ? list1[j] : j;
+        const float2 xy = gxy[t];                                                     // the key point's own x, y (k_match_grid)
+        cnt++; m12[i1] = gitems[t]; prev[2 * i1] = xy.x; prev[2 * i1 + 1] = xy.y;     // :515-517
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
@@ -871,15 +898,15 @@ __global__ __launch_bounds__(MS_T) void k_match_select(MatchParams M) { match_se
 __global__ __launch_bounds__(MS_T) void k_match_select_big(MatchParams M) { match_select_body<true>(M); }
 
 #define MS_LDS_BUDGET (158 * 1024)
-size_t orbhip_match_select_ints(int cap, int lvl0_cap) { return (size_t)4 * cap + (size_t)4 * lvl0_cap + ORBHIP_HISTO_LENGTH + 8; }
-bool orbhip_match_select_big(int cap, int lvl0_cap)
+size_t orbhip_match_select_ints(int tab_cap, int lvl0_cap) { return (size_t)2 * tab_cap + (size_t)lvl0_cap + ORBHIP_HISTO_LENGTH + 8; }
+bool orbhip_match_select_big(int tab_cap, int lvl0_cap)
 {
     const char* env = getenv("ORBHIP_SELECT_BIG");                       // tests: 1 = the device-memory form at any size (read per call: tests switch inside one process)
     const bool force = env && env[0] == '1';
-    return force || sizeof(int) * orbhip_match_select_ints(cap, lvl0_cap) > MS_LDS_BUDGET;
+    return force || sizeof(int) * orbhip_match_select_ints(tab_cap, lvl0_cap) > MS_LDS_BUDGET;
 }
 void orbhip_launch_match_select(const MatchParams& M, int nslots, hipStream_t s)
 {
     if (M.big_ws) hipLaunchKernelGGL(k_match_select_big, dim3(nslots, 1, 1), dim3(MS_T, 1, 1), 0, s, M);
-    else hipLaunchKernelGGL(k_match_select, dim3(nslots, 1, 1), dim3(MS_T, 1, 1), sizeof(int) * orbhip_match_select_ints(M.cap, M.lvl0_cap), s, M);
+    else hipLaunchKernelGGL(k_match_select, dim3(nslots, 1, 1), dim3(MS_T, 1, 1), sizeof(int) * orbhip_match_select_ints(M.tab_cap, M.lvl0_cap), s, M);
 }
