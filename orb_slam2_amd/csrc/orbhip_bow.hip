@@ -311,16 +311,6 @@ __device__ __forceinline__ unsigned long long bm_argmin_mask(int d, unsigned lon
 
 // slot of a batched launch that block `block` belongs to: pref[s] = first block of slot s (ascending, pref[nslots] = grid size); uniform -> scalar loads
 __device__ __forceinline__ int bm_batch_slot(const int* pref, int nslots, int block) { int s = 0; while (s + 1 < nslots && block >= pref[s + 1]) s++; return s; }
-// a pair's parameter block through the scalar cache (scalar_ptr, orbhip_internal.h): the address is the same for every lane, the host wrote the block before the
-// launch and no kernel writes it.  Copied member by member from the constant address space, the block sits in SGPRs and its pointers are global ones, exactly
-// like a by-value kernel argument (fetched as plain dwords the pointers would be generic: flat loads, a 64-bit address per lane).
-template <typename T> __device__ __forceinline__ T param_block(const T* p)
-{
-    T v;
-    __builtin_memcpy(&v, scalar_ptr(p), sizeof(T));
-    return v;
-}
-
 // wave64 minimum with DPP row shifts / broadcasts (6 dependent VALU steps against the 9 ballots of bm_argmin_mask); result broadcast from lane 63
 __device__ __forceinline__ int bm_wave_min(int v)
 {

@@ -142,9 +142,12 @@ bool orbhip_bind_thread_to_node(int node);          // binds the CALLING thread 
 void orbhip_launch_stereo(const StereoParams& T, int nslots, int max_left, hipStream_t s, bool rows_ready = false);
 void orbhip_launch_stereo_rows(const StereoParams& T, int nslots, hipStream_t s);     // the right frame's row table alone (needs only T.R, geom, im_h, cap, row_*)
 
-struct ProjParams {         // projection-guided search core (ORBmatcher.cc:45-129 and :1328-1470), one frame
+// Projection-guided search core (ORBmatcher.cc:45-129 and :1328-1470): the block of one frame (slot).  A call's blocks form a table in device memory that the host
+// writes before the launch and the kernels only read (param_block); a one-frame call is a table of one.  Filled by proj_block (orbhip_search.hip) alone.
+struct ProjParams {
     const orbhip_keypoint* kp; const uint8_t* desc; const float* u_right; int n;           // the Frame being searched
     float min_x, min_y, max_x, max_y;                                   // Frame::mnMinX .. mnMaxY (Frame.cc:436-464)
+    float gw_inv, gh_inv;                                               // mfGridElementWidthInv / HeightInv (Frame.cc:101-102), divided on the host
     const int* grid_start; const int* grid_items; const float2* grid_xy;                   // 64x48 grid over ALL keypoints
     const orbhip_proj_query* q; const uint8_t* qdesc; int nq;
     // projection on the device (orbhip_project_search_*): with pts != nullptr query i is DERIVED from pts[i] under *proj by k_proj_candidates, which also
@@ -157,8 +160,9 @@ struct ProjParams {         // projection-guided search core (ORBmatcher.cc:45-1
     int* big_ws;                // 4 n ints of device memory when the select kernel's per-feature tables do not fit LDS (orbhip_proj_select_big(n)); nullptr otherwise
 };
 bool orbhip_proj_select_big(int n);       // the per-feature tables of k_proj_select exceed the LDS budget: the caller provides ProjParams::big_ws
-void orbhip_launch_proj(const ProjParams& J, hipStream_t s, bool fp_contract = false);      // fp_contract: the fused projection (ORBHIP_FP_CONTRACT)
-void orbhip_launch_proj_batch(const ProjParams* d_slots, int nslots, int max_nq, int max_n, float gwInv, float ghInv, hipStream_t s);
+// both kernels over the nslots blocks at d_slots; max_nq / max_n: the largest slot's (big_ws is set for every slot or for none: orbhip_proj_select_big(max_n)); fp_contract: the fused projection (ORBHIP_FP_CONTRACT)
+void orbhip_launch_proj(const ProjParams* d_slots, int nslots, int max_nq, int max_n, hipStream_t s, bool fp_contract = false);
+// Best-in-window search core: the block of one key frame (slot), in a table like ProjParams'.  Filled by best_block (orbhip_search.hip) alone.
 struct BestParams {
     const orbhip_keypoint* kp; const uint8_t* desc; const float* u_right; const float* inv_level_sigma2;
     const int* grid_start; const int* grid_items; const float2* grid_xy;        // ordered bucket table over ALL key points (k_match_grid, grid_all_levels)
@@ -168,8 +172,8 @@ struct BestParams {
     float min_x, gw_inv;        // left image bound and grid columns per pixel of the table's grid (gw_inv = 0: scan the whole table)
     const unsigned long long* skip; int skip_bit;     // (orbhip_project_best_in_window_shared) bit skip_bit of skip[iq] set: the query is not searched; nullptr: all are
 };
-void orbhip_launch_best_in_window(const BestParams& B, hipStream_t s, bool fp_contract = false);
-void orbhip_launch_best_in_window_batch(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s, bool fp_contract = false);
+// d_pref[s] = first workgroup of slot s (four queries each), nblocks = their sum
+void orbhip_launch_best_in_window(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s, bool fp_contract = false);
 size_t orbhip_proj_select_lds(int n);
 
 // kernel launchers (orbhip_kernels_extract.hip / orbhip_kernels_match.hip)
@@ -231,7 +235,7 @@ __device__ __forceinline__ int orbhip_writelane(int v, int dst_lane, int old)
 }
 // One element of a read-only table at an index every lane agrees on, through the SCALAR cache (s_load: the result lands in SGPRs and counts on lgkmcnt).
 // As an ordinary load the compiler makes it a vector load - the kernel also stores to global memory, so it may not assume the table constant - and waiting
-// for a vector load means waiting for every LDS-DMA request issued before it (vmcnt returns in order).  Tables only: written by the host before the launch (orbhip_kernels_extract.hip's row tables, orbhip_bow.hip's parameter blocks).
+// for a vector load means waiting for every LDS-DMA request issued before it (vmcnt returns in order).  Tables only: written by the host before the launch (orbhip_kernels_extract.hip's row tables, the parameter blocks of orbhip_bow.hip and orbhip_kernels_proj.hip).
 #ifdef __HIPCC__
 #define ORBHIP_CONSTANT __attribute__((address_space(4)))
 #else
@@ -244,6 +248,15 @@ template <typename T> __device__ __forceinline__ const ORBHIP_CONSTANT T* scalar
     return (const ORBHIP_CONSTANT T*)(((unsigned long long)hi << 32) | lo);
 }
 template <typename T> __device__ __forceinline__ T scalar_load(const T* p) { return *scalar_ptr(p); }
+// A parameter block of a table launch (orbhip_bow.hip's pairs, orbhip_kernels_proj.hip's slots) through the scalar cache: the address is the same for every lane, the
+// host wrote the block before the launch and no kernel writes it.  Copied member by member from the constant address space, the block sits in SGPRs and its pointers
+// are global ones, exactly like a by-value kernel argument (fetched as plain dwords the pointers would be generic: flat loads, a 64-bit address per lane).
+template <typename T> __device__ __forceinline__ T param_block(const T* p)
+{
+    T v;
+    __builtin_memcpy(&v, scalar_ptr(p), sizeof(T));
+    return v;
+}
 // ---- the calling thread's arena for the host-pointer ("stateless") matcher entry points: every array of a call is laid out in ONE device
 // allocation (grow-only, per thread) whose head mirrors a pinned host block, so that all inputs travel in one copy and all outputs in one copy
 #include <vector>

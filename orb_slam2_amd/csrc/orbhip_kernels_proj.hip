@@ -140,8 +140,9 @@ template <bool FC> __device__ __forceinline__ bool pj_project(const orbhip_proje
     return true;
 }
 
-template <bool FC> __device__ __forceinline__ void proj_candidates_body(const ProjParams& J, float gwInv, float ghInv)
+template <bool FC> __device__ __forceinline__ void proj_candidates_body(const ProjParams& J)
 {
+    const float gwInv = J.gw_inv, ghInv = J.gh_inv;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int iq = blockIdx.x * 4 + wave;
     if (iq >= J.nq) return;
@@ -231,11 +232,11 @@ template <bool FC> __device__ __forceinline__ void proj_candidates_body(const Pr
     if (lane < PJ_K) J.top[PJ_REC * iq + lane] = out;
     if (lane == PJ_K) J.top[PJ_REC * iq + PJ_K] = more ? 1u : 0u;
 }
-__global__ __launch_bounds__(256) void k_proj_candidates(ProjParams J, float gwInv, float ghInv) { proj_candidates_body<false>(J, gwInv, ghInv); }
+// Every frame (camera slot) of a call in one launch, a one-frame call being a table of one: blockIdx.y = slot.  The parameter blocks lie in device memory, written by
+// the host before the launch and only read here; a slot's block comes through the scalar cache (param_block, orbhip_internal.h) and sits in SGPRs like a kernel argument.
+__global__ __launch_bounds__(256) void k_proj_candidates(const ProjParams* Js) { const ProjParams J = param_block(Js + blockIdx.y); proj_candidates_body<false>(J); }
 // the same with the fused projection (ORBHIP_FP_CONTRACT): a kernel of its own, so that the canonical one's code is what it was
-__global__ __launch_bounds__(256) void k_proj_candidates_fc(ProjParams J, float gwInv, float ghInv) { proj_candidates_body<true>(J, gwInv, ghInv); }
-// several frames (camera slots) per launch: blockIdx.y = slot, its parameters come from a table in device memory (given queries: no projection)
-__global__ __launch_bounds__(256) void k_proj_candidates_batch(const ProjParams* Js, float gwInv, float ghInv) { const ProjParams J = Js[blockIdx.y]; proj_candidates_body<false>(J, gwInv, ghInv); }
+__global__ __launch_bounds__(256) void k_proj_candidates_fc(const ProjParams* Js) { const ProjParams J = param_block(Js + blockIdx.y); proj_candidates_body<true>(J); }
 
 
 // The order-dependent loop, 256 queries per step on all four waves.  A query's decision (its first recorded candidates nobody has claimed) is final once
@@ -449,11 +450,9 @@ template <bool BIG> __device__ __forceinline__ void proj_select_body(const ProjP
     __syncthreads();
     for (int i = tid; i < n; i += PJ_T) { J.feature_query[i] = s_fq[i]; if (J.blocked_out) J.blocked_out[i] = (unsigned char)s_blocked[i]; }
 }
-__global__ __launch_bounds__(PJ_T) void k_proj_select(ProjParams J) { proj_select_body<false>(J); }
-__global__ __launch_bounds__(PJ_T) void k_proj_select_big(ProjParams J) { proj_select_body<true>(J); }
-// one workgroup per camera slot (big_ws is set for every slot or for none: the launcher decides on the largest slot)
-__global__ __launch_bounds__(PJ_T) void k_proj_select_batch(const ProjParams* Js) { const ProjParams J = Js[blockIdx.x]; proj_select_body<false>(J); }
-__global__ __launch_bounds__(PJ_T) void k_proj_select_batch_big(const ProjParams* Js) { const ProjParams J = Js[blockIdx.x]; proj_select_body<true>(J); }
+// one workgroup per slot of the table (big_ws is set for every slot or for none: the host decides on the largest slot, like the launcher)
+__global__ __launch_bounds__(PJ_T) void k_proj_select(const ProjParams* Js) { const ProjParams J = param_block(Js + blockIdx.x); proj_select_body<false>(J); }
+__global__ __launch_bounds__(PJ_T) void k_proj_select_big(const ProjParams* Js) { const ProjParams J = param_block(Js + blockIdx.x); proj_select_body<true>(J); }
 
 #define PJ_LDS_BUDGET (150 * 1024)
 size_t orbhip_proj_select_lds(int n) { return sizeof(int) * ((size_t)4 * n + ORBHIP_HISTO_LENGTH + 16); }
@@ -464,22 +463,14 @@ bool orbhip_proj_select_big(int n)
     return force || orbhip_proj_select_lds(n) > PJ_LDS_BUDGET;
 }
 
-void orbhip_launch_proj(const ProjParams& J, hipStream_t s, bool fp_contract)
-{
-    const float gwInv = (float)ORBHIP_GRID_COLS / (float)(J.max_x - J.min_x), ghInv = (float)ORBHIP_GRID_ROWS / (float)(J.max_y - J.min_y);
-    if (J.nq > 0 && fp_contract) hipLaunchKernelGGL(k_proj_candidates_fc, dim3((J.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, J, gwInv, ghInv);
-    else if (J.nq > 0) hipLaunchKernelGGL(k_proj_candidates, dim3((J.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, J, gwInv, ghInv);
-    if (J.big_ws) hipLaunchKernelGGL(k_proj_select_big, dim3(1, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(0), s, J);
-    else hipLaunchKernelGGL(k_proj_select, dim3(1, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(J.n), s, J);
-}
-
-
-void orbhip_launch_proj_batch(const ProjParams* d_slots, int nslots, int max_nq, int max_n, float gwInv, float ghInv, hipStream_t s)
+// d_slots: the call's table in device memory; the candidates' grid covers the slot with most queries, the select kernel's LDS the slot with most features
+void orbhip_launch_proj(const ProjParams* d_slots, int nslots, int max_nq, int max_n, hipStream_t s, bool fp_contract)
 {
     if (nslots <= 0) return;
-    if (max_nq > 0) hipLaunchKernelGGL(k_proj_candidates_batch, dim3((max_nq + 3) / 4, nslots, 1), dim3(256, 1, 1), 0, s, d_slots, gwInv, ghInv);
-    if (orbhip_proj_select_big(max_n)) hipLaunchKernelGGL(k_proj_select_batch_big, dim3(nslots, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(0), s, d_slots);
-    else hipLaunchKernelGGL(k_proj_select_batch, dim3(nslots, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(max_n), s, d_slots);
+    if (max_nq > 0 && fp_contract) hipLaunchKernelGGL(k_proj_candidates_fc, dim3((max_nq + 3) / 4, nslots, 1), dim3(256, 1, 1), 0, s, d_slots);
+    else if (max_nq > 0) hipLaunchKernelGGL(k_proj_candidates, dim3((max_nq + 3) / 4, nslots, 1), dim3(256, 1, 1), 0, s, d_slots);
+    if (orbhip_proj_select_big(max_n)) hipLaunchKernelGGL(k_proj_select_big, dim3(nslots, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(0), s, d_slots);
+    else hipLaunchKernelGGL(k_proj_select, dim3(nslots, 1, 1), dim3(PJ_T, 1, 1), orbhip_proj_select_lds(max_n), s, d_slots);
 }
 
 // ------------------------------------------------------------------------------------------------ best candidate in a window
@@ -557,34 +548,20 @@ template <bool FC> __device__ __forceinline__ void best_in_window_body(const Bes
     }
     if (lane == 0) { B.best_idx[iq] = bidx; B.best_dist[iq] = best; }
 }
-__global__ __launch_bounds__(256) void k_best_in_window(BestParams B)
-{
-    best_in_window_body<false>(B, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
-}
-// several key frames in one launch (orbhip_search_best_in_window_batch): parameter blocks in device memory, pref[s] = first block of slot s
-__global__ __launch_bounds__(256) void k_best_in_window_batch(const BestParams* Bs, const int* pref, int nslots)
+// Every key frame (slot) of a call in one launch, a one-frame call being a table of one: parameter blocks in device memory (written by the host before the launch,
+// only read here, fetched through the scalar cache), pref[s] = first block of slot s
+template <bool FC> __device__ __forceinline__ void best_in_window_slots(const BestParams* Bs, const int* pref, int nslots)
 {
     int sl = 0; while (sl + 1 < nslots && (int)blockIdx.x >= pref[sl + 1]) sl++;
-    best_in_window_body<false>(Bs[sl], ((int)blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
+    const BestParams B = param_block(Bs + sl);
+    best_in_window_body<FC>(B, ((int)blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
 }
-// the same two with the fused forms (ORBHIP_FP_CONTRACT): kernels of their own, so that the canonical ones' code is what it was
-__global__ __launch_bounds__(256) void k_best_in_window_fc(BestParams B)
-{
-    best_in_window_body<true>(B, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
-}
-__global__ __launch_bounds__(256) void k_best_in_window_batch_fc(const BestParams* Bs, const int* pref, int nslots)
-{
-    int sl = 0; while (sl + 1 < nslots && (int)blockIdx.x >= pref[sl + 1]) sl++;
-    best_in_window_body<true>(Bs[sl], ((int)blockIdx.x - pref[sl]) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63);
-}
+__global__ __launch_bounds__(256) void k_best_in_window(const BestParams* Bs, const int* pref, int nslots) { best_in_window_slots<false>(Bs, pref, nslots); }
+// the same with the fused forms (ORBHIP_FP_CONTRACT): a kernel of its own, so that the canonical one's code is what it was
+__global__ __launch_bounds__(256) void k_best_in_window_fc(const BestParams* Bs, const int* pref, int nslots) { best_in_window_slots<true>(Bs, pref, nslots); }
 
-void orbhip_launch_best_in_window(const BestParams& B, hipStream_t s, bool fp_contract)
+void orbhip_launch_best_in_window(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s, bool fp_contract)
 {
-    if (B.nq > 0 && fp_contract) hipLaunchKernelGGL(k_best_in_window_fc, dim3((B.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, B);
-    else if (B.nq > 0) hipLaunchKernelGGL(k_best_in_window, dim3((B.nq + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, B);
-}
-void orbhip_launch_best_in_window_batch(const BestParams* d_slots, const int* d_pref, int nslots, int nblocks, hipStream_t s, bool fp_contract)
-{
-    if (nblocks > 0 && fp_contract) hipLaunchKernelGGL(k_best_in_window_batch_fc, dim3(nblocks, 1, 1), dim3(256, 1, 1), 0, s, d_slots, d_pref, nslots);
-    else if (nblocks > 0) hipLaunchKernelGGL(k_best_in_window_batch, dim3(nblocks, 1, 1), dim3(256, 1, 1), 0, s, d_slots, d_pref, nslots);
+    if (nblocks > 0 && fp_contract) hipLaunchKernelGGL(k_best_in_window_fc, dim3(nblocks, 1, 1), dim3(256, 1, 1), 0, s, d_slots, d_pref, nslots);
+    else if (nblocks > 0) hipLaunchKernelGGL(k_best_in_window, dim3(nblocks, 1, 1), dim3(256, 1, 1), 0, s, d_slots, d_pref, nslots);
 }

@@ -1,9 +1,8 @@
-// orbhip_search.hip — host side of the matcher searches of liborbhip.so: projection-guided and best-in-window searches (single frame, batch,
-// shared / held), the stateless matcher entry points and the relocalisation candidates.  Kernels: orbhip_kernels_proj.hip, orbhip_kernels_match.hip.
+// orbhip_search.hip — host side of the matcher searches of liborbhip.so.  The projection-guided and the best-in-window search have ONE routine each that takes a
+// list of slots and does the whole call (search_by_projection_slots, search_best_in_window_slots): every entry point - one frame as host arrays or resident on a
+// context, batch, shared - checks its own arguments, states them as slots and calls it; orbhip_project_best_in_window_held searches a slot the shared call left.
+// Then the stateless matcher entry points and the relocalisation candidates.  Kernels: orbhip_kernels_proj.hip, orbhip_kernels_match.hip.
 #include "orbhip_ctx.h"
-
-// the slots orbhip_project_best_in_window_shared left in the calling thread's scratch (valid while orbhip_tl_held_valid, orbhip_api.hip)
-static thread_local struct HeldSlots { int device = -1; size_t floor = 0; std::vector<BestParams> B; std::vector<int> live_of_slot; } g_held;
 
 // Frame::AssignFeaturesToGrid over ALL key points of nslots frames kp[slot][cap] (counts d_n[slot]) into the tables at [slot]: k_match_grid with grid_all_levels
 void launch_feature_grid(const orbhip_keypoint* kp, const int* d_n, int cap, const orbhip_bounds& b, int* grid_start, int* grid_items, float2* grid_xy,
@@ -59,63 +58,138 @@ static orbhip_status frame_args(orbhip_ctx* c, int frame, int n, int use_u_right
     return ORBHIP_OK;
 }
 
+// One frame (slot) of a projection-guided search call: queries given, or (points != nullptr) derived on the device from nq map points under *proj
+// (orbhip_project_search_*: k_proj_candidates also writes them to queries_out, if asked for)
+struct ProjSlotIn {
+    SearchFrame F; const uint8_t* blocked;                                              // blocked: optional
+    const orbhip_proj_query* queries; const uint8_t* query_desc; int nq;
+    const orbhip_projection* proj; const orbhip_map_point* points; orbhip_proj_query* queries_out;
+    int32_t* feature_query; int* nmatches;
+};
+// where a slot's arrays lie on the device
+struct ProjDev {
+    const orbhip_keypoint* kp; const uint8_t* desc; const float* u_right; const int* grid_start; const int* grid_items; const float2* grid_xy;
+    orbhip_proj_query* q; const uint8_t* qdesc; const orbhip_map_point* pts; const orbhip_projection* proj; const unsigned char* blocked;
+    int* feature_query; int* nmatches; unsigned* cand; int* ncand; unsigned* top; int* events; int* big_ws;
+};
+// the slot's block of the table the kernels read (the only place that fills one)
+static ProjParams proj_block(const ProjSlotIn& S, const ProjDev& D, int mode, float nnratio, int th_high, int check_ori)
+{
+    const orbhip_bounds& b = S.F.bounds;
+    ProjParams J; memset(&J, 0, sizeof J);
+    J.kp = D.kp; J.desc = D.desc; J.u_right = D.u_right; J.n = S.F.n; J.min_x = b.min_x; J.min_y = b.min_y; J.max_x = b.max_x; J.max_y = b.max_y;
+    J.gw_inv = (float)ORBHIP_GRID_COLS / (float)(b.max_x - b.min_x); J.gh_inv = (float)ORBHIP_GRID_ROWS / (float)(b.max_y - b.min_y);      // as orbhip_launch_match_grid lays the grid out
+    J.grid_start = D.grid_start; J.grid_items = D.grid_items; J.grid_xy = D.grid_xy;
+    J.q = D.q; J.qdesc = D.qdesc; J.nq = S.nq; J.pts = D.pts; J.proj = D.proj; J.q_out = D.q;
+    J.cand = D.cand; J.ncand = D.ncand; J.cand_stride = S.F.n; J.top = D.top;
+    J.blocked_in = D.blocked; J.blocked_out = nullptr; J.feature_query = D.feature_query; J.nmatches = D.nmatches; J.events = D.events;
+    J.mode = mode; J.nnratio = nnratio; J.th_high = th_high; J.check_ori = check_ori; J.big_ws = D.big_ws;
+    return J;
+}
+
 // (ORBHIP_RECORD / TestRecord, the emulation-only capture of the calls below: orbhip_internal.h)
 
-// queries given (P == nullptr) or derived on the device from map points under *P (orbhip_project_search_*): `queries` is then nullptr and nq = the point count
+// The entry point behind a call of the two slot routines.  ONE_FRAME: one slot, which may be a resident frame - the call then runs on its context's stream, with
+// the grid built behind its extraction if that is ready; BATCH: the _batch entry points, slots of host arrays; SHARED: orbhip_project_best_in_window_shared
+enum SlotForm { ONE_FRAME, BATCH, SHARED };
+
+// Every slot of a call in one pass, a one-frame call being one slot: ONE arena - the parameter table, each live slot's inputs at their own size, then every answer
+// (what the download carries back: no input lies between two answers), then the kernels' work space - one copy each way, one launch of each kernel over the table
+// (the order-dependent one runs a workgroup per slot).
+static orbhip_status search_by_projection_slots(int nslots, ProjSlotIn* slots, int mode, float nnratio, int th_high, int check_ori, SlotForm form)
+{
+    OrbApiTimer api_timer;
+    const bool batch = form == BATCH;
+    if (mode != 0 && mode != 1) return fail(ORBHIP_ERR_INVALID, "bad argument");
+    std::vector<int> live;
+    int cap = 1, qcap = 1;
+    for (int s = 0; s < nslots; s++) {
+        const ProjSlotIn& S = slots[s]; const int n = S.F.n;
+        if (n < 0 || S.nq < 0 || !S.nmatches || (n > 0 && (!S.F.kps || !S.F.desc || !S.feature_query)) || (S.nq > 0 && ((!S.queries && !S.points) || !S.query_desc)) || (S.points && !projection_ok(S.proj)))
+            return batch ? fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s) : fail(ORBHIP_ERR_INVALID, "bad argument");
+        *S.nmatches = 0;
+        for (int i = 0; i < n; i++) S.feature_query[i] = -1;
+        if (S.points) gated_out(S.queries_out, S.nq);
+        cap = std::max(cap, n); qcap = std::max(qcap, S.nq);
+        if (n > 0 && S.nq > 0) live.push_back(s);
+    }
+    if (live.empty()) return ORBHIP_OK;
+    const SearchFrame& F0 = slots[live[0]].F;
+    if (F0.on_host && cap >= (1 << 19)) return fail(ORBHIP_ERR_UNSUPPORTED, "too many features");
+    if (batch && (size_t)nslots * qcap * cap * sizeof(unsigned) > ((size_t)2 << 30)) return fail(ORBHIP_ERR_UNSUPPORTED, "candidate lists of %d slots x %d queries x %d features exceed 2 GB: split the batch", nslots, qcap, cap);
+    if (F0.on_host && !device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    HIPCHK(hipSetDevice(F0.device));
+    const hipStream_t ts = F0.on_host ? orbhip_thread_stream(F0.device) : F0.stream;
+    const int NL = (int)live.size();
+    const bool fc = fp_contract_of(slots[live[0]].proj);                               // (only a one-frame call brings points)
+    int max_n = 1, max_nq = 1;                                                         // the launch is sized by the slots with work (cap / qcap above: the preconditions' view of all slots)
+    for (int k = 0; k < NL; k++) { max_n = std::max(max_n, slots[live[k]].F.n); max_nq = std::max(max_nq, slots[live[k]].nq); }
+    // the select kernel's per-feature tables in device memory: for every slot or for none.  orbhip_launch_proj asks the same question of the same max_n (and reads
+    // ORBHIP_SELECT_BIG again): the two answers must agree, or a kernel finds no big_ws / sizes its LDS for none
+    const bool big = orbhip_proj_select_big(max_n);
+    std::vector<ProjParams> hJ(NL); std::vector<ProjDev> D(NL); std::vector<int> hn(NL), hnm(NL, 0);
+    std::vector<orbhip_projection> hP(NL);                                             // the slots' projections as the device reads them (bare kind)
+    std::vector<size_t> noff(NL + 1, 0), qoff(NL + 1, 0), coff(NL + 1, 0);             // the slots' places in the shared work arrays: features, queries, candidates before them
+    for (int k = 0; k < NL; k++) {
+        const ProjSlotIn& S = slots[live[k]];
+        hn[k] = S.F.n; if (S.points) hP[k] = bare_projection(*S.proj);
+        noff[k + 1] = noff[k] + (size_t)S.F.n; qoff[k + 1] = qoff[k] + (size_t)S.nq; coff[k + 1] = coff[k] + (size_t)S.nq * S.F.n;
+    }
+    ProjParams* dJ = nullptr; int *dn = nullptr, *dnm = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dev = nullptr, *dbig = nullptr; float2* dgxy = nullptr; unsigned *dcand = nullptr, *dtop = nullptr;
+    const hipError_t e = arena_call(F0.device, ts, [&](Arena& A) {
+        A.io(&dJ, (size_t)NL, (const ProjParams*)hJ.data(), (size_t)NL);
+        A.io(&dn, (size_t)NL, (const int*)hn.data(), (size_t)NL);
+        for (int k = 0; k < NL; k++) {                                                  // every slot's inputs ...
+            const ProjSlotIn& S = slots[live[k]]; ProjDev& d = D[k]; const size_t n = (size_t)S.F.n, nq = (size_t)S.nq;
+            d.kp = S.F.kps; d.desc = S.F.desc; d.u_right = S.F.u_right;                 // (host arrays: replaced by their copies)
+            if (S.F.on_host) { arena_in(A, &d.kp, S.F.kps, n); arena_in(A, &d.desc, S.F.desc, n * 32); if (S.F.u_right) arena_in(A, &d.u_right, S.F.u_right, n); }
+            arena_in(A, &d.qdesc, S.query_desc, nq * 32);
+            if (S.points) { arena_in(A, &d.pts, S.points, nq); arena_in(A, &d.proj, &hP[k], 1); }
+            else A.io(&d.q, nq, S.queries, nq);
+            if (S.blocked) arena_in(A, &d.blocked, S.blocked, n);
+        }
+        A.io(&dnm, (size_t)NL, (const int*)nullptr, 0, hnm.data(), (size_t)NL);        // ... then every answer: the match counts (k_proj_select writes every slot's), feature_query, the derived queries
+        for (int k = 0; k < NL; k++) A.io(&D[k].feature_query, (size_t)hn[k], (const int*)nullptr, 0, slots[live[k]].feature_query, (size_t)hn[k]);
+        for (int k = 0; k < NL; k++) { const ProjSlotIn& S = slots[live[k]]; if (S.points) A.io(&D[k].q, (size_t)S.nq, (const orbhip_proj_query*)nullptr, 0, S.queries_out, S.queries_out ? (size_t)S.nq : 0); }
+        A.take(&dgs, (size_t)NL * (ORBHIP_GRID_CELLS + 1)); A.take(&dgi, noff[NL]); A.take(&dgxy, noff[NL]); A.take(&dnc, qoff[NL]); A.take(&dev, qoff[NL]);
+        A.take(&dcand, coff[NL]); A.take(&dtop, qoff[NL] * 5);
+        if (big) A.take(&dbig, 4 * noff[NL]);
+        for (int k = 0; k < NL; k++) {                                                  // (hJ is read when the arena is uploaded, after this pass has filled in the addresses)
+            const ProjSlotIn& S = slots[live[k]]; ProjDev& d = D[k];
+            const bool own = !S.F.grid_start;                                           // the slot does not bring its grid: built below
+            d.grid_start = own ? dgs + (size_t)k * (ORBHIP_GRID_CELLS + 1) : S.F.grid_start; d.grid_items = own ? dgi + noff[k] : S.F.grid_items; d.grid_xy = own ? dgxy + noff[k] : S.F.grid_xy;
+            d.nmatches = dnm + k; d.ncand = dnc + qoff[k]; d.events = dev + qoff[k]; d.cand = dcand + coff[k]; d.top = dtop + qoff[k] * 5; d.big_ws = big ? dbig + 4 * noff[k] : nullptr;
+            hJ[k] = proj_block(S, d, mode, nnratio, th_high, check_ori);
+        }
+    }, [&] {
+        for (int k = 0; k < NL; k++) {                                                  // Frame::AssignFeaturesToGrid of every slot that needs it
+            const SearchFrame& F = slots[live[k]].F;
+            if (!F.grid_start) launch_feature_grid(D[k].kp, dn + k, F.n, F.bounds, dgs + (size_t)k * (ORBHIP_GRID_CELLS + 1), dgi + noff[k], dgxy + noff[k], 1, 0, ts);
+            if (F.want_grid) *F.want_grid = true;
+        }
+        orbhip_launch_proj(dJ, NL, max_nq, max_n, ts, fc);
+    });
+    if (e != hipSuccess) {
+        for (int k = 0; k < NL; k++) { const ProjSlotIn& S = slots[live[k]]; for (int i = 0; i < S.F.n; i++) S.feature_query[i] = -1; if (S.points) gated_out(S.queries_out, S.nq); }
+        return fail(ORBHIP_ERR_HIP, "%s: %s", batch ? "search_by_projection_batch" : F0.on_host ? "search_by_projection" : "search_by_projection_frame", hipGetErrorString(e));
+    }
+    for (int k = 0; k < NL; k++) *slots[live[k]].nmatches = hnm[k];
+    ORBHIP_RECORD(if (!batch) for (int k = 0; k < NL; k++) {
+        const ProjSlotIn& S = slots[live[k]]; const SearchFrame& F = S.F;
+        if (!S.points) continue;
+        TestRecord R(1); const float par[2] = {nnratio, (float)0}; const int ipar[3] = {th_high, check_ori, hnm[k]};
+        R.put(F.kps, F.n); R.put(F.desc, (size_t)F.n * 32); R.put(F.u_right, F.n); R.put(S.blocked, F.n); R.put(&F.bounds, 1); R.put(S.proj, 1); R.put(S.points, S.nq); R.put(S.query_desc, (size_t)S.nq * 32);
+        R.put(par, 2); R.put(ipar, 3); R.put(S.feature_query, F.n);
+    });
+    return ORBHIP_OK;
+}
+// one frame: queries given (P == nullptr) or derived on the device from map points under *P (orbhip_project_search_*): `queries` is then nullptr and nq = the point count
 static orbhip_status search_by_projection(const SearchFrame& F, const uint8_t* blocked, const orbhip_proj_query* queries, const uint8_t* query_desc, int nq,
                                           const orbhip_projection* P, const orbhip_map_point* points, orbhip_proj_query* queries_out,
                                           int mode, float nnratio, int th_high, int check_ori, int32_t* feature_query, int* nmatches)
 {
-    OrbApiTimer api_timer;
-    const int n = F.n;
-    if (nq < 0 || !nmatches || (n > 0 && !feature_query) || (nq > 0 && ((!queries && !points) || !query_desc)) || (mode != 0 && mode != 1) || (points && !projection_ok(P)))
-        return fail(ORBHIP_ERR_INVALID, "bad argument");
-    *nmatches = 0;
-    for (int i = 0; i < n; i++) feature_query[i] = -1;
-    if (points) gated_out(queries_out, nq);
-    if (n == 0 || nq == 0) return ORBHIP_OK;
-    if (F.on_host && n >= (1 << 19)) return fail(ORBHIP_ERR_UNSUPPORTED, "too many features");
-    if (F.on_host && !device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
-    HIPCHK(hipSetDevice(F.device));
-    const hipStream_t s = F.on_host ? orbhip_thread_stream(F.device) : F.stream;
-    const orbhip_keypoint* dk = F.kps; const uint8_t* dd = F.desc; const float* dur = F.u_right;      // (host arrays: replaced by their copies)
-    uint8_t* dqd = nullptr; unsigned char* dbl_in = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dfq = nullptr, *dev = nullptr, *dbig = nullptr;
-    float2* dgxy = nullptr; orbhip_proj_query* dq = nullptr; unsigned* dcand = nullptr; unsigned* dtop = nullptr;
-    orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
-    const int hn[2] = {n, 0}; int hres[2] = {0, 0};
-    const orbhip_projection hP = points ? bare_projection(*P) : orbhip_projection{};
-    const hipError_t e = arena_call(F.device, s, [&](Arena& A) {
-        if (F.on_host) { arena_in(A, &dk, F.kps, n); arena_in(A, &dd, F.desc, (size_t)n * 32); }
-        A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32);
-        if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, &hP, 1); A.io(&dq, nq, (const orbhip_proj_query*)nullptr, 0, queries_out, queries_out ? nq : 0); }
-        else A.io(&dq, nq, queries, nq);
-        if (F.on_host && F.u_right) arena_in(A, &dur, F.u_right, n);
-        if (blocked) A.io(&dbl_in, n, blocked, n);
-        A.io(&dn, 8, hn, 2, hres, 2);                         // [0] = n in, [1] = the return value out
-        A.io(&dfq, n, (const int*)nullptr, 0, feature_query, n);
-        A.take(&dgs, ORBHIP_GRID_CELLS + 1); A.take(&dgi, n); A.take(&dgxy, n); A.take(&dnc, nq); A.take(&dev, nq);
-        A.take(&dcand, (size_t)nq * n); A.take(&dtop, (size_t)nq * 5);
-        if (orbhip_proj_select_big(n)) A.take(&dbig, (size_t)4 * n);      // the select kernel's per-feature tables when they do not fit LDS
-    }, [&] {
-        const int* gs = F.grid_start; const int* gi = F.grid_items; const float2* gxy = F.grid_xy;
-        if (!gs) { launch_feature_grid(dk, dn, n, F.bounds, dgs, dgi, dgxy, 1, 0, s); gs = dgs; gi = dgi; gxy = dgxy; }
-        if (F.want_grid) *F.want_grid = true;
-        ProjParams J; memset(&J, 0, sizeof J);
-        J.kp = dk; J.desc = dd; J.u_right = dur; J.n = n; J.min_x = F.bounds.min_x; J.min_y = F.bounds.min_y; J.max_x = F.bounds.max_x; J.max_y = F.bounds.max_y; J.grid_start = gs; J.grid_items = gi; J.grid_xy = gxy;
-        J.q = dq; J.qdesc = dqd; J.nq = nq; J.cand = dcand; J.ncand = dnc; J.cand_stride = n; J.top = dtop;
-        J.pts = dpts; J.proj = dP; J.q_out = dq;
-        J.blocked_in = dbl_in; J.blocked_out = nullptr; J.feature_query = dfq; J.nmatches = dn + 1; J.events = dev;
-        J.mode = mode; J.nnratio = nnratio; J.th_high = th_high; J.check_ori = check_ori; J.big_ws = dbig;
-        orbhip_launch_proj(J, s, fp_contract_of(P));
-    });
-    if (e != hipSuccess) return fail(ORBHIP_ERR_HIP, F.on_host ? "search_by_projection: %s" : "search_by_projection_frame: %s", hipGetErrorString(e));
-    *nmatches = hres[1];
-    ORBHIP_RECORD(if (points) {
-        TestRecord R(1); const float par[2] = {nnratio, (float)0}; const int ipar[3] = {th_high, check_ori, hres[1]};
-        R.put(F.kps, n); R.put(F.desc, (size_t)n * 32); R.put(F.u_right, n); R.put(blocked, n); R.put(&F.bounds, 1); R.put(P, 1); R.put(points, nq); R.put(query_desc, (size_t)nq * 32);
-        R.put(par, 2); R.put(ipar, 3); R.put(feature_query, n);
-    });
-    return ORBHIP_OK;
+    ProjSlotIn S{F, blocked, queries, query_desc, nq, P, points, queries_out, feature_query, nmatches};
+    return search_by_projection_slots(1, &S, mode, nnratio, th_high, check_ori, ONE_FRAME);
 }
 extern "C" orbhip_status orbhip_search_by_projection_bounds(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right,
                                                      const uint8_t* blocked, int n, const orbhip_bounds* bounds,
@@ -149,111 +223,167 @@ extern "C" orbhip_status orbhip_project_search_frame(orbhip_ctx* c, int frame, i
     return search_by_projection(F, blocked, nullptr, point_desc, np, np > 0 ? proj : nullptr, np > 0 ? points : nullptr, queries_out, 1, nnratio, th_high, check_ori, feature_query, nmatches);
 }
 
-// Several frames in one pass: every per-slot array lives at [slot][cap] of one arena (one copy each way), the order-dependent kernel runs
-// one workgroup per slot.
+// Several frames in one pass: the slots of the C ABI as slots of the routine above (one bounds for all)
 extern "C" orbhip_status orbhip_search_by_projection_batch(int device, int nslots, orbhip_proj_slot* slots, const orbhip_bounds* bounds,
                                                            int mode, float nnratio, int th_high, int check_ori)
 {
-    OrbApiTimer api_timer;
     if (nslots < 0 || (nslots > 0 && !slots) || !bounds || !(bounds->max_x > bounds->min_x) || !(bounds->max_y > bounds->min_y) || (mode != 0 && mode != 1))
         return fail(ORBHIP_ERR_INVALID, "bad argument");
-    int cap = 1, qcap = 1; bool any_ur = false, any_bl = false, work = false;
+    std::vector<ProjSlotIn> in((size_t)nslots);
     for (int s = 0; s < nslots; s++) {
         orbhip_proj_slot& S = slots[s];
-        if (S.n < 0 || S.nq < 0 || (S.n > 0 && (!S.kps || !S.desc || !S.feature_query)) || (S.nq > 0 && (!S.queries || !S.query_desc))) return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
-        S.nmatches = 0;
-        for (int i = 0; i < S.n; i++) S.feature_query[i] = -1;
-        cap = std::max(cap, S.n); qcap = std::max(qcap, S.nq);
-        any_ur = any_ur || S.u_right; any_bl = any_bl || S.blocked; work = work || (S.n > 0 && S.nq > 0);
+        in[s] = ProjSlotIn{SearchFrame{device, nullptr, S.n, *bounds, true, S.kps, S.desc, S.u_right}, S.blocked, S.queries, S.query_desc, S.nq, nullptr, nullptr, nullptr, S.feature_query, &S.nmatches};
     }
-    if (!work) return ORBHIP_OK;
-    if (cap >= (1 << 19)) return fail(ORBHIP_ERR_UNSUPPORTED, "too many features");
-    if ((size_t)nslots * qcap * cap * sizeof(unsigned) > ((size_t)2 << 30)) return fail(ORBHIP_ERR_UNSUPPORTED, "candidate lists of %d slots x %d queries x %d features exceed 2 GB: split the batch", nslots, qcap, cap);
-    if (!device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    int *dn = nullptr, *dnm = nullptr, *dgs = nullptr, *dgi = nullptr, *dnc = nullptr, *dev = nullptr, *dbig = nullptr; float2* dgxy = nullptr; unsigned *dcand = nullptr, *dtop = nullptr; ProjParams* dJ = nullptr;
-    std::vector<int> hn(nslots), hnm(nslots, 0); std::vector<ProjParams> hJ(nslots);
-    std::vector<float> no_ur(any_ur ? cap : 0, -1.0f); std::vector<uint8_t> no_bl(any_bl ? cap : 0, 0);
-    for (int s = 0; s < nslots; s++) hn[s] = slots[s].n;
-    const size_t C = (size_t)cap, Q = (size_t)qcap;
-    const hipError_t e = arena_call(device, ts, [&](Arena& A) {
-        A.io(&dJ, (size_t)nslots, (const ProjParams*)hJ.data(), (size_t)nslots);
-        A.io(&dn, (size_t)nslots, (const int*)hn.data(), (size_t)nslots);
-        A.io(&dnm, (size_t)nslots, (const int*)hnm.data(), (size_t)nslots, hnm.data(), (size_t)nslots);
-        for (int s = 0; s < nslots; s++) {                                        // [slot][cap] / [slot][qcap] blocks, each slot's rows from its own host arrays
-            const orbhip_proj_slot& S = slots[s];
-            orbhip_keypoint* k = nullptr; uint8_t *d = nullptr, *qd = nullptr; orbhip_proj_query* q = nullptr; float* ur = nullptr; unsigned char* bl = nullptr; int* fq = nullptr;
-            A.io(&k, C, S.kps, (size_t)S.n); A.io(&d, C * 32, S.desc, (size_t)S.n * 32); A.io(&q, Q, S.queries, (size_t)S.nq); A.io(&qd, Q * 32, S.query_desc, (size_t)S.nq * 32);
-            if (any_ur) A.io(&ur, C, S.u_right ? S.u_right : no_ur.data(), (size_t)S.n);
-            if (any_bl) A.io(&bl, C, (const unsigned char*)(S.blocked ? S.blocked : no_bl.data()), (size_t)S.n);
-            A.io(&fq, C, (const int*)nullptr, 0, S.feature_query, (size_t)S.n);
-            ProjParams& J = hJ[s]; memset(&J, 0, sizeof J);
-            J.kp = k; J.desc = d; J.u_right = S.u_right ? ur : nullptr; J.n = S.n; J.q = q; J.qdesc = qd; J.nq = S.nq; J.blocked_in = S.blocked ? bl : nullptr; J.feature_query = fq;
+    return search_by_projection_slots(nslots, in.data(), mode, nnratio, th_high, check_ori, BATCH);
+}
+// One key frame (slot) of a best-in-window search call; inv_level_sigma2 / nlevels: mvInvLevelSigma2 of the frame's extractor (a context's frame: its own).
+// Queries given, or (points != nullptr) derived on the device from nq map points under *proj (orbhip_project_best_in_window_*), written to queries_out if asked for.
+struct BestSlotIn {
+    SearchFrame F; const float* inv_level_sigma2; int nlevels;
+    const orbhip_best_query* queries; const uint8_t* query_desc; int nq; const orbhip_projection* proj; const orbhip_map_point* points; orbhip_best_query* queries_out;
+    int32_t* best_idx; int32_t* best_dist;
+};
+// where a slot's arrays lie on the device
+struct BestDev {
+    const orbhip_keypoint* kp; const uint8_t* desc; const float* u_right; const float* inv_level_sigma2; const int* grid_start; const int* grid_items; const float2* grid_xy;      // the key frame: what a held slot keeps
+    const orbhip_best_query* q; const uint8_t* qdesc; const orbhip_map_point* pts; const orbhip_projection* proj; const unsigned long long* skip; orbhip_best_query* q_out; int* best_idx; int* best_dist;
+};
+// the slot's block of the table the kernels read (the only place that fills one)
+static BestParams best_block(const BestDev& D, const orbhip_bounds& b, int nq, int chi2_gate, int skip_bit)
+{
+    BestParams B; memset(&B, 0, sizeof B);
+    B.kp = D.kp; B.desc = D.desc; B.u_right = D.u_right; B.inv_level_sigma2 = D.inv_level_sigma2; B.grid_start = D.grid_start; B.grid_items = D.grid_items; B.grid_xy = D.grid_xy;
+    B.q = D.q; B.qdesc = D.qdesc; B.nq = nq; B.chi2_gate = chi2_gate; B.pts = D.pts; B.proj = D.proj; B.q_out = D.q_out; B.best_idx = D.best_idx; B.best_dist = D.best_dist;
+    B.min_x = b.min_x; B.gw_inv = (float)ORBHIP_GRID_COLS / (float)(b.max_x - b.min_x);      // as orbhip_launch_match_grid lays the grid out
+    B.skip = D.skip; B.skip_bit = skip_bit;
+    return B;
+}
+// the slots orbhip_project_best_in_window_shared left in the calling thread's scratch (valid while orbhip_tl_held_valid, orbhip_api.hip)
+static thread_local struct HeldSlots { int device = -1; size_t floor = 0; std::vector<BestDev> D; std::vector<orbhip_bounds> bounds; std::vector<int> live_of_slot; } g_held;
+
+// Every key frame of a call in one pass (Fuse over all targets), a one-frame call being one slot: [slot][cap] key point / grid blocks in one arena; the feature grids
+// of all slots are built by ONE k_match_grid launch when the slots share their image bounds (key frames of one camera do), the searches by one launch over all queries.
+// SHARED: every slot's queries are slots[0]'s (points / query_desc / nq: uploaded once); skip: see orbhip_project_best_in_window_shared
+static orbhip_status search_best_in_window_slots(int device, int nslots, BestSlotIn* slots, int chi2_gate, SlotForm form, const uint64_t* skip)
+{
+    OrbApiTimer api_timer;
+    const bool shared = form == SHARED;
+    if (shared) {
+        orbhip_tl_held_valid = false;                                                   // whatever an earlier call left held is not THIS call's (also when nothing is live below)
+        if (nslots > 64) return fail(ORBHIP_ERR_INVALID, "at most 64 slots share one set of points");
+        for (int s = 1; s < nslots; s++)
+            if (slots[s].nq != slots[0].nq || (slots[0].nq > 0 && (slots[s].points != slots[0].points || slots[s].query_desc != slots[0].query_desc || !slots[s].points)))        // (no points: nothing to name)
+                return fail(ORBHIP_ERR_INVALID, "slot %d does not name slot 0's points", s);
+    }
+    std::vector<int> live;
+    int cap = 1, fc = -1;                                    // fc: the slots' ORBHIP_FP_CONTRACT (one launch: every slot with points must agree)
+    for (int s = 0; s < nslots; s++) {
+        BestSlotIn& S = slots[s]; const orbhip_bounds& b = S.F.bounds;
+        if (S.F.n < 0 || S.nq < 0 || (S.nq > 0 && ((!S.queries && !S.points) || !S.query_desc || !S.best_idx || !S.best_dist)) || (S.F.n > 0 && (!S.F.kps || !S.F.desc)) ||
+            !(b.max_x > b.min_x) || !(b.max_y > b.min_y) || (chi2_gate && (!S.inv_level_sigma2 || S.nlevels < 1)) || (S.nq > 0 && S.points && !projection_ok(S.proj)))
+            return form == ONE_FRAME ? fail(ORBHIP_ERR_INVALID, "bad argument") : fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
+        if (S.nq > 0 && S.points) {
+            if (fc >= 0 && fc != (int)fp_contract_of(S.proj)) return fail(ORBHIP_ERR_INVALID, "slot %d: the slots of one call mix ORBHIP_FP_CONTRACT and its absence", s);
+            fc = fp_contract_of(S.proj);
         }
-        A.take(&dgs, (size_t)nslots * (ORBHIP_GRID_CELLS + 1)); A.take(&dgi, nslots * C); A.take(&dgxy, nslots * C); A.take(&dnc, nslots * Q); A.take(&dev, nslots * Q);
-        A.take(&dcand, nslots * Q * C); A.take(&dtop, nslots * Q * 5);
-        if (orbhip_proj_select_big(cap)) A.take(&dbig, nslots * 4 * C);      // the select kernel's per-feature tables when the largest slot's do not fit LDS
-        for (int s = 0; s < nslots; s++) {                                        // (hJ is read when the arena is uploaded, after this pass has filled in the addresses)
-            ProjParams& J = hJ[s];
-            J.big_ws = dbig ? dbig + s * 4 * C : nullptr;
-            J.min_x = bounds->min_x; J.min_y = bounds->min_y; J.max_x = bounds->max_x; J.max_y = bounds->max_y;
-            J.grid_start = dgs + (size_t)s * (ORBHIP_GRID_CELLS + 1); J.grid_items = dgi + s * C; J.grid_xy = dgxy + s * C;
-            J.cand = dcand + s * Q * C; J.ncand = dnc + s * Q; J.cand_stride = cap; J.top = dtop + s * Q * 5; J.nmatches = dnm + s; J.events = dev + s * Q;
-            J.mode = mode; J.nnratio = nnratio; J.th_high = th_high; J.check_ori = check_ori;
+        no_match(S.best_idx, S.best_dist, S.nq);
+        if (S.points) gated_out(S.queries_out, S.nq);
+        if (S.F.n == 0 || S.nq == 0) continue;
+        live.push_back(s); cap = std::max(cap, S.F.n);
+    }
+    if (live.empty()) {
+        if (shared) {                                                                   // held: a slot without key points answers -1 / 256; one whose key frame never travelled (no points were offered) cannot answer (-2)
+            g_held.device = device; g_held.floor = 0; g_held.D.clear(); g_held.bounds.clear(); g_held.live_of_slot.assign((size_t)nslots, -1);
+            for (int s = 0; s < nslots; s++) if (slots[s].F.n > 0) g_held.live_of_slot[(size_t)s] = -2;
+            orbhip_tl_held_valid = true;
+        }
+        return ORBHIP_OK;
+    }
+    const SearchFrame& F0 = slots[live[0]].F;
+    if (F0.on_host && !device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
+    HIPCHK(hipSetDevice(device));
+    const hipStream_t ts = F0.on_host ? orbhip_thread_stream(device) : F0.stream;
+    cap = (cap + 63) & ~63;                                  // 64 key points = 7 x 256 bytes: the arena's 256-byte blocks then lie exactly cap records apart ([slot][cap])
+    const int NL = (int)live.size(); const size_t C = (size_t)cap;
+    const bool ready = F0.grid_start != nullptr;             // (one slot: a resident frame whose grid was built behind its extraction)
+    bool same_bounds = true;
+    for (int k = 1; k < NL; k++) same_bounds = same_bounds && !memcmp(&slots[live[k]].F.bounds, &F0.bounds, sizeof(orbhip_bounds));
+    std::vector<BestParams> hB(NL); std::vector<BestDev> D(NL); std::vector<int> pref(NL + 1, 0), hn(NL);
+    std::vector<orbhip_projection> hP(NL);                   // the slots' projections as the device reads them (bare kind)
+    for (int k = 0; k < NL; k++) if (slots[live[k]].points) hP[k] = bare_projection(*slots[live[k]].proj);
+    for (int k = 0; k < NL; k++) { pref[k + 1] = pref[k] + (slots[live[k]].nq + 3) / 4; hn[k] = slots[live[k]].F.n; }
+    BestParams* dB = nullptr; int *dpref = nullptr, *dn = nullptr, *dgs = nullptr, *dgi = nullptr; float2* dgxy = nullptr;
+    size_t held_floor = 0;
+    const hipError_t e = arena_call(device, ts, [&](Arena& A) {
+        A.io(&dB, (size_t)NL, (const BestParams*)hB.data(), (size_t)NL);
+        A.io(&dpref, (size_t)NL + 1, (const int*)pref.data(), (size_t)NL + 1);
+        A.io(&dn, (size_t)NL, (const int*)hn.data(), (size_t)NL);
+        for (int k = 0; k < NL; k++) {                                                  // [slot][cap] key points first: k_match_grid indexes them by slot
+            const SearchFrame& F = slots[live[k]].F;
+            D[k].kp = F.kps;                                                            // (host arrays: replaced by their copies, here and below)
+            if (F.on_host) { orbhip_keypoint* dk = nullptr; A.io(&dk, C, F.kps, (size_t)F.n); D[k].kp = dk; }
+        }
+        for (int k = 0; k < NL; k++) {                                                  // every slot's inputs ...
+            const BestSlotIn& S = slots[live[k]]; const SearchFrame& F = S.F; BestDev& d = D[k]; const size_t n = (size_t)F.n, nq = (size_t)S.nq;
+            d.desc = F.desc; d.u_right = F.u_right;
+            if (F.on_host) { arena_in(A, &d.desc, F.desc, n * 32); if (F.u_right) arena_in(A, &d.u_right, F.u_right, n); }
+            if (shared) {
+                if (k == 0) {
+                    arena_in(A, &d.qdesc, S.query_desc, nq * 32); arena_in(A, &d.pts, S.points, nq);
+                    if (skip) arena_in(A, &d.skip, reinterpret_cast<const unsigned long long*>(skip), nq);
+                }
+                d.qdesc = D[0].qdesc; d.pts = D[0].pts; d.skip = D[0].skip; arena_in(A, &d.proj, &hP[k], 1);
+            } else {
+                arena_in(A, &d.qdesc, S.query_desc, nq * 32);
+                if (S.points) { arena_in(A, &d.pts, S.points, nq); arena_in(A, &d.proj, &hP[k], 1); }
+                else arena_in(A, &d.q, S.queries, nq);
+            }
+            if (S.inv_level_sigma2 && S.nlevels > 0) arena_in(A, &d.inv_level_sigma2, S.inv_level_sigma2, (size_t)S.nlevels);
+        }
+        for (int k = 0; k < NL; k++) {                                                  // ... then every slot's answers, contiguous: the download is one small copy
+            const BestSlotIn& S = slots[live[k]];
+            A.io(&D[k].best_idx, (size_t)S.nq, (const int*)nullptr, 0, S.best_idx, (size_t)S.nq); A.io(&D[k].best_dist, (size_t)S.nq, (const int*)nullptr, 0, S.best_dist, (size_t)S.nq);
+            if (S.points && S.queries_out) A.io(&D[k].q_out, (size_t)S.nq, (const orbhip_best_query*)nullptr, 0, S.queries_out, (size_t)S.nq);
+        }
+        if (!ready) { A.take(&dgs, (size_t)NL * (ORBHIP_GRID_CELLS + 1)); A.take(&dgi, NL * C); A.take(&dgxy, NL * C); }
+        for (int k = 0; k < NL; k++) {                                                  // (hB is read when the arena is uploaded, after this pass has filled in the addresses)
+            const BestSlotIn& S = slots[live[k]]; BestDev& d = D[k];
+            d.grid_start = ready ? S.F.grid_start : dgs + (size_t)k * (ORBHIP_GRID_CELLS + 1); d.grid_items = ready ? S.F.grid_items : dgi + k * C; d.grid_xy = ready ? S.F.grid_xy : dgxy + k * C;
+            hB[k] = best_block(d, S.F.bounds, S.nq, chi2_gate, live[k]);
+        }
+        if (shared) {                                                                   // room for the held entry's block and queries behind everything: it never reallocates
+            held_floor = A.off; uint8_t* pad = nullptr; A.take(&pad, (size_t)slots[live[0]].nq * (sizeof(orbhip_map_point) + 32 + 8) + 4096 + 512);
         }
     }, [&] {
-        // Frame::AssignFeaturesToGrid of every slot: the grid kernel indexes [slot][stride]
-        for (int s = 0; s < nslots; s++) launch_feature_grid(hJ[s].kp, dn + s, cap, *bounds, dgs + (size_t)s * (ORBHIP_GRID_CELLS + 1), dgi + s * C, dgxy + s * C, 1, 0, ts);
-        const float gwInv = (float)ORBHIP_GRID_COLS / (bounds->max_x - bounds->min_x), ghInv = (float)ORBHIP_GRID_ROWS / (bounds->max_y - bounds->min_y);
-        orbhip_launch_proj_batch(dJ, nslots, qcap, cap, gwInv, ghInv, ts);
+        if (!ready) for (int k = 0; k < (same_bounds ? 1 : NL); k++) launch_feature_grid(D[0].kp, dn, cap, slots[live[k]].F.bounds, dgs, dgi, dgxy, same_bounds ? NL : 1, k, ts);
+        for (int k = 0; k < NL; k++) if (slots[live[k]].F.want_grid) *slots[live[k]].F.want_grid = true;
+        orbhip_launch_best_in_window(dB, dpref, NL, pref[NL], ts, fc == 1);
     });
-    if (e != hipSuccess) return fail(ORBHIP_ERR_HIP, "search_by_projection_batch: %s", hipGetErrorString(e));
-    for (int s = 0; s < nslots; s++) slots[s].nmatches = hnm[s];
+    if (e != hipSuccess) {
+        for (int k = 0; k < NL; k++) { const BestSlotIn& S = slots[live[k]]; no_match(S.best_idx, S.best_dist, S.nq); if (S.points) gated_out(S.queries_out, S.nq); }
+        return fail(ORBHIP_ERR_HIP, "%s: %s", form != ONE_FRAME ? "search_best_in_window_batch" : F0.on_host ? "search_best_in_window" : "search_best_in_window_frame", hipGetErrorString(e));
+    }
+    ORBHIP_RECORD(if (form == BATCH) for (int k = 0; k < NL; k++) {
+        const BestSlotIn& S = slots[live[k]]; const SearchFrame& F = S.F;
+        if (!S.points) continue;
+        TestRecord R(2); const int ipar[1] = {chi2_gate};
+        R.put(F.kps, F.n); R.put(F.desc, (size_t)F.n * 32); R.put(F.u_right, F.n); R.put(&F.bounds, 1); R.put(S.inv_level_sigma2, S.nlevels); R.put(S.proj, 1);
+        R.put(S.points, S.nq); R.put(S.query_desc, (size_t)S.nq * 32); R.put(ipar, 1); R.put(S.best_idx, S.nq); R.put(S.best_dist, S.nq);
+    });
+    if (shared) {                                                                       // the slots stay where they are for orbhip_project_best_in_window_held
+        g_held.device = device; g_held.floor = held_floor; g_held.D = D; g_held.bounds.resize((size_t)NL); g_held.live_of_slot.assign((size_t)nslots, -1);
+        for (int k = 0; k < NL; k++) { g_held.bounds[(size_t)k] = slots[live[k]].F.bounds; g_held.live_of_slot[(size_t)live[k]] = k; }
+        orbhip_tl_held_valid = true;
+    }
     return ORBHIP_OK;
 }
-
-// inv_level_sigma2 / nlevels: mvInvLevelSigma2 of the frame's extractor (a context's frame: its own)
+// one frame: queries given (P == nullptr) or derived on the device from map points under *P
 static orbhip_status search_best_in_window(const SearchFrame& F, const float* inv_level_sigma2, int nlevels, const orbhip_best_query* queries, const uint8_t* query_desc, int nq,
                                            const orbhip_projection* P, const orbhip_map_point* points, orbhip_best_query* queries_out,
                                            int chi2_gate, int32_t* best_idx, int32_t* best_dist)
 {
-    OrbApiTimer api_timer;
-    const int n = F.n;
-    if (nq < 0 || (nq > 0 && ((!queries && !points) || !query_desc || !best_idx || !best_dist)) || (chi2_gate && (!inv_level_sigma2 || nlevels < 1)) || (points && !projection_ok(P)))
-        return fail(ORBHIP_ERR_INVALID, "bad argument");
-    no_match(best_idx, best_dist, nq);
-    if (points) gated_out(queries_out, nq);
-    if (n == 0 || nq == 0) return ORBHIP_OK;
-    if (F.on_host && !device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
-    HIPCHK(hipSetDevice(F.device));
-    const hipStream_t s = F.on_host ? orbhip_thread_stream(F.device) : F.stream;
-    const orbhip_keypoint* dk = F.kps; const uint8_t* dd = F.desc; const float* dur = F.u_right;      // (host arrays: replaced by their copies)
-    uint8_t* dqd = nullptr; float* dsg = nullptr; int *dn = nullptr, *dgs = nullptr, *dgi = nullptr, *dbi = nullptr, *dbd = nullptr;
-    float2* dgxy = nullptr; orbhip_best_query* dq = nullptr; orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
-    const int hn[2] = {n, 0};
-    const orbhip_projection hP = points ? bare_projection(*P) : orbhip_projection{};
-    const hipError_t e = arena_call(F.device, s, [&](Arena& A) {
-        if (F.on_host) { arena_in(A, &dk, F.kps, n); arena_in(A, &dd, F.desc, (size_t)n * 32); }
-        A.io(&dqd, (size_t)nq * 32, query_desc, (size_t)nq * 32); A.io(&dn, 8, hn, 2);
-        if (points) { A.io(&dpts, nq, points, nq); A.io(&dP, 1, &hP, 1); if (queries_out) A.io(&dq, nq, (const orbhip_best_query*)nullptr, 0, queries_out, nq); }
-        else A.io(&dq, nq, queries, nq);
-        if (F.on_host && F.u_right) arena_in(A, &dur, F.u_right, n);
-        if (inv_level_sigma2 && nlevels > 0) A.io(&dsg, nlevels, inv_level_sigma2, nlevels);
-        A.io(&dbi, nq, (const int*)nullptr, 0, best_idx, nq); A.io(&dbd, nq, (const int*)nullptr, 0, best_dist, nq);
-        A.take(&dgs, ORBHIP_GRID_CELLS + 1); A.take(&dgi, n); A.take(&dgxy, n);
-    }, [&] {
-        const int* gs = F.grid_start; const int* gi = F.grid_items; const float2* gxy = F.grid_xy;
-        if (!gs) { launch_feature_grid(dk, dn, n, F.bounds, dgs, dgi, dgxy, 1, 0, s); gs = dgs; gi = dgi; gxy = dgxy; }
-        if (F.want_grid) *F.want_grid = true;
-        BestParams B; memset(&B, 0, sizeof B);
-        B.kp = dk; B.desc = dd; B.u_right = dur; B.inv_level_sigma2 = dsg; B.grid_start = gs; B.grid_items = gi; B.grid_xy = gxy;
-        B.q = dq; B.qdesc = dqd; B.nq = nq; B.chi2_gate = chi2_gate; B.best_idx = dbi; B.best_dist = dbd;
-        B.pts = dpts; B.proj = dP; B.q_out = points ? dq : nullptr;
-        B.min_x = F.bounds.min_x; B.gw_inv = (float)ORBHIP_GRID_COLS / (float)(F.bounds.max_x - F.bounds.min_x);      // as orbhip_launch_match_grid lays the grid out
-        orbhip_launch_best_in_window(B, s, fp_contract_of(P));
-    });
-    return e == hipSuccess ? ORBHIP_OK : fail(ORBHIP_ERR_HIP, F.on_host ? "search_best_in_window: %s" : "search_best_in_window_frame: %s", hipGetErrorString(e));
+    BestSlotIn S{F, inv_level_sigma2, nlevels, queries, query_desc, nq, P, points, queries_out, best_idx, best_dist};
+    return search_best_in_window_slots(F.device, 1, &S, chi2_gate, ONE_FRAME, nullptr);
 }
 extern "C" orbhip_status orbhip_search_best_in_window_bounds(int device, const orbhip_keypoint* kps, const uint8_t* desc, const float* u_right, int n, const orbhip_bounds* bounds,
                                                       const float* inv_level_sigma2, int nlevels, const orbhip_best_query* queries, const uint8_t* query_desc, int nq,
@@ -276,129 +406,9 @@ extern "C" orbhip_status orbhip_search_best_in_window_frame(orbhip_ctx* c, int f
     return search_best_in_window(F, c->is2.data(), c->L, queries, query_desc, nq, nullptr, nullptr, nullptr, chi2_gate, best_idx, best_dist);
 }
 
-// Several key frames in one pass (Fuse over all targets): [slot][cap] key point / descriptor / grid blocks in one arena; the feature grids of all slots are
-// built by ONE k_match_grid launch when the slots share their image bounds (key frames of one camera do), the searches by one launch over all queries.
-// Queries given per slot, or derived on the device from the slot's map points under its projection (orbhip_project_best_in_window_batch).
-struct BestSlotIn {
-    const orbhip_keypoint* kps; const uint8_t* desc; const float* u_right; int n; orbhip_bounds bounds; const float* inv_level_sigma2; int nlevels;
-    const orbhip_best_query* queries; const uint8_t* query_desc; int nq; const orbhip_projection* proj; const orbhip_map_point* points;
-    int32_t* best_idx; int32_t* best_dist;
-};
-// shared: every slot's queries are slots[0]'s (points / query_desc / nq: uploaded once); skip: see orbhip_project_best_in_window_shared
-static orbhip_status search_best_in_window_batch_impl(int device, int nslots, BestSlotIn* slots, int chi2_gate, bool shared = false, const uint64_t* skip = nullptr)
-{
-    OrbApiTimer api_timer;
-    if (shared) {
-        orbhip_tl_held_valid = false;                                                   // whatever an earlier call left held is not THIS call's (also when nothing is live below)
-        if (nslots > 64) return fail(ORBHIP_ERR_INVALID, "at most 64 slots share one set of points");
-        for (int s = 1; s < nslots; s++)
-            if (slots[s].nq != slots[0].nq || (slots[0].nq > 0 && (slots[s].points != slots[0].points || slots[s].query_desc != slots[0].query_desc || !slots[s].points)))        // (no points: nothing to name)
-                return fail(ORBHIP_ERR_INVALID, "slot %d does not name slot 0's points", s);
-    }
-    std::vector<int> live;
-    int cap = 1, fc = -1;                                    // fc: the slots' ORBHIP_FP_CONTRACT (one launch: every slot with points must agree)
-    for (int s = 0; s < nslots; s++) {
-        BestSlotIn& S = slots[s];
-        if (S.n < 0 || S.nq < 0 || (S.nq > 0 && ((!S.queries && !S.points) || !S.query_desc || !S.best_idx || !S.best_dist)) || (S.n > 0 && (!S.kps || !S.desc)) ||
-            !(S.bounds.max_x > S.bounds.min_x) || !(S.bounds.max_y > S.bounds.min_y) || (chi2_gate && (!S.inv_level_sigma2 || S.nlevels < 1)) || (S.nq > 0 && S.points && !projection_ok(S.proj)))
-            return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
-        if (S.nq > 0 && S.points) {
-            if (fc >= 0 && fc != (int)fp_contract_of(S.proj)) return fail(ORBHIP_ERR_INVALID, "slot %d: the slots of one call mix ORBHIP_FP_CONTRACT and its absence", s);
-            fc = fp_contract_of(S.proj);
-        }
-        no_match(S.best_idx, S.best_dist, S.nq);
-        if (S.n == 0 || S.nq == 0) continue;
-        live.push_back(s); cap = std::max(cap, S.n);
-    }
-    if (live.empty()) {
-        if (shared) {                                                                   // held: a slot without key points answers -1 / 256; one whose key frame never travelled (no points were offered) cannot answer (-2)
-            g_held.device = device; g_held.floor = 0; g_held.B.clear(); g_held.live_of_slot.assign((size_t)nslots, -1);
-            for (int s = 0; s < nslots; s++) if (slots[s].n > 0) g_held.live_of_slot[(size_t)s] = -2;
-            orbhip_tl_held_valid = true;
-        }
-        return ORBHIP_OK;
-    }
-    if (!device_present()) return fail(ORBHIP_ERR_HIP, "no HIP device available: no CPU fallback");
-    HIPCHK(hipSetDevice(device));
-    hipStream_t ts = orbhip_thread_stream(device);
-    cap = (cap + 63) & ~63;                                  // 64 key points = 7 x 256 bytes: the arena's 256-byte blocks then lie exactly cap records apart ([slot][cap])
-    const int NL = (int)live.size(); const size_t C = (size_t)cap;
-    bool same_bounds = true;
-    for (int k = 1; k < NL; k++) same_bounds = same_bounds && !memcmp(&slots[live[k]].bounds, &slots[live[0]].bounds, sizeof(orbhip_bounds));
-    std::vector<BestParams> hB(NL); std::vector<int> pref(NL + 1, 0), hn(NL);
-    std::vector<orbhip_projection> hP(NL);                   // the slots' projections as the device reads them (bare kind)
-    for (int k = 0; k < NL; k++) if (slots[live[k]].points) hP[k] = bare_projection(*slots[live[k]].proj);
-    for (int k = 0; k < NL; k++) { pref[k + 1] = pref[k] + (slots[live[k]].nq + 3) / 4; hn[k] = slots[live[k]].n; }
-    BestParams* dB = nullptr; int *dpref = nullptr, *dn = nullptr, *dgs = nullptr, *dgi = nullptr; float2* dgxy = nullptr; orbhip_keypoint* dk0 = nullptr;
-    uint8_t* dqd0 = nullptr; orbhip_map_point* dpts0 = nullptr; unsigned long long* dskip = nullptr;          // shared: the one copy of the points
-    size_t held_floor = 0;
-    const hipError_t e = arena_call(device, ts, [&](Arena& A) {
-        A.io(&dB, (size_t)NL, (const BestParams*)hB.data(), (size_t)NL);
-        A.io(&dpref, (size_t)NL + 1, (const int*)pref.data(), (size_t)NL + 1);
-        A.io(&dn, (size_t)NL, (const int*)hn.data(), (size_t)NL);
-        for (int k = 0; k < NL; k++) {                                                  // [slot][cap] key points first: k_match_grid indexes them by slot
-            orbhip_keypoint* dk = nullptr; A.io(&dk, C, slots[live[k]].kps, (size_t)slots[live[k]].n);
-            if (k == 0) dk0 = dk;
-            hB[k].kp = dk;
-        }
-        for (int k = 0; k < NL; k++) {                                                  // every slot's inputs ...
-            const BestSlotIn& S = slots[live[k]]; BestParams& B = hB[k];
-            uint8_t *dd = nullptr, *dqd = nullptr; float *dur = nullptr, *dsg = nullptr; orbhip_best_query* dq = nullptr; orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr;
-            A.io(&dd, (size_t)S.n * 32, S.desc, (size_t)S.n * 32);
-            if (shared) {
-                if (k == 0) {
-                    A.io(&dqd0, (size_t)S.nq * 32, S.query_desc, (size_t)S.nq * 32); A.io(&dpts0, S.nq, S.points, S.nq);
-                    if (skip) A.io(&dskip, S.nq, reinterpret_cast<const unsigned long long*>(skip), S.nq);
-                }
-                dqd = dqd0; dpts = dpts0; A.io(&dP, 1, &hP[k], 1);
-            } else {
-                A.io(&dqd, (size_t)S.nq * 32, S.query_desc, (size_t)S.nq * 32);
-                if (S.points) { A.io(&dpts, S.nq, S.points, S.nq); A.io(&dP, 1, &hP[k], 1); }
-                else A.io(&dq, S.nq, S.queries, S.nq);
-            }
-            if (S.u_right) A.io(&dur, S.n, S.u_right, S.n);
-            if (S.inv_level_sigma2 && S.nlevels > 0) A.io(&dsg, S.nlevels, S.inv_level_sigma2, S.nlevels);
-            B.desc = dd; B.u_right = dur; B.inv_level_sigma2 = dsg; B.q = dq; B.qdesc = dqd; B.nq = S.nq; B.chi2_gate = chi2_gate;
-            B.pts = dpts; B.proj = dP; B.q_out = nullptr;
-            B.skip = shared ? dskip : nullptr; B.skip_bit = live[k];
-            B.min_x = S.bounds.min_x; B.gw_inv = (float)ORBHIP_GRID_COLS / (float)(S.bounds.max_x - S.bounds.min_x);
-        }
-        for (int k = 0; k < NL; k++) {                                                  // ... then every slot's answers, contiguous: the download is one small copy
-            const BestSlotIn& S = slots[live[k]]; BestParams& B = hB[k];
-            int *dbi = nullptr, *dbd = nullptr;
-            A.io(&dbi, S.nq, (const int*)nullptr, 0, S.best_idx, S.nq); A.io(&dbd, S.nq, (const int*)nullptr, 0, S.best_dist, S.nq);
-            B.best_idx = dbi; B.best_dist = dbd;
-        }
-        A.take(&dgs, (size_t)NL * (ORBHIP_GRID_CELLS + 1)); A.take(&dgi, NL * C); A.take(&dgxy, NL * C);
-        for (int k = 0; k < NL; k++) { hB[k].grid_start = dgs + (size_t)k * (ORBHIP_GRID_CELLS + 1); hB[k].grid_items = dgi + k * C; hB[k].grid_xy = dgxy + k * C; }
-        if (shared) {                                                                   // room for the held entry's queries behind everything: it never reallocates
-            held_floor = A.off; uint8_t* pad = nullptr; A.take(&pad, (size_t)slots[live[0]].nq * (sizeof(orbhip_map_point) + 32 + 8) + 4096);
-        }
-    }, [&] {
-        for (int k = 0; k < (same_bounds ? 1 : NL); k++) launch_feature_grid(dk0, dn, cap, slots[live[k]].bounds, dgs, dgi, dgxy, same_bounds ? NL : 1, k, ts);
-        orbhip_launch_best_in_window_batch(dB, dpref, NL, pref[NL], ts, fc == 1);
-    });
-    if (e != hipSuccess) {
-        for (int k = 0; k < NL; k++) no_match(slots[live[k]].best_idx, slots[live[k]].best_dist, slots[live[k]].nq);
-        return fail(ORBHIP_ERR_HIP, "search_best_in_window_batch: %s", hipGetErrorString(e));
-    }
-    ORBHIP_RECORD(if (!shared) for (int k = 0; k < NL; k++) {
-        const BestSlotIn& S = slots[live[k]];
-        if (!S.points) continue;
-        TestRecord R(2); const int ipar[1] = {chi2_gate};
-        R.put(S.kps, S.n); R.put(S.desc, (size_t)S.n * 32); R.put(S.u_right, S.n); R.put(&S.bounds, 1); R.put(S.inv_level_sigma2, S.nlevels); R.put(S.proj, 1);
-        R.put(S.points, S.nq); R.put(S.query_desc, (size_t)S.nq * 32); R.put(ipar, 1); R.put(S.best_idx, S.nq); R.put(S.best_dist, S.nq);
-    });
-    if (shared) {                                                                       // the slots stay where they are for orbhip_project_best_in_window_held
-        g_held.device = device; g_held.floor = held_floor; g_held.B = hB; g_held.live_of_slot.assign((size_t)nslots, -1);
-        for (int k = 0; k < NL; k++) g_held.live_of_slot[(size_t)live[k]] = k;
-        orbhip_tl_held_valid = true;
-    }
-    return ORBHIP_OK;
-}
 // One slot of the calling thread's last orbhip_project_best_in_window_shared call searched again with other points: its key frame, descriptors and
-// grid table are still in the thread's scratch - only the points travel (ORBmatcher.cc's FuseBatch: the points whose descriptor an earlier target's
-// MapPoint::Replace changed, MapPoint.cc:177-215)
+// grid table are still in the thread's scratch - only the points travel, with a table of one block, above what is held (ORBmatcher.cc's FuseBatch: the points
+// whose descriptor an earlier target's MapPoint::Replace changed, MapPoint.cc:177-215)
 extern "C" orbhip_status orbhip_project_best_in_window_held(int device, int slot, const orbhip_projection* proj, const orbhip_map_point* points, const uint8_t* point_desc, int np,
                                                             int chi2_gate, int32_t* best_idx, int32_t* best_dist)
 {
@@ -412,16 +422,16 @@ extern "C" orbhip_status orbhip_project_best_in_window_held(int device, int slot
     if (k < 0 || np == 0) return ORBHIP_OK;                                             // (a slot without key points or a call without points: nothing to search)
     HIPCHK(hipSetDevice(device));
     hipStream_t ts = orbhip_thread_stream(device);
-    uint8_t* dqd = nullptr; orbhip_map_point* dpts = nullptr; orbhip_projection* dP = nullptr; int *dbi = nullptr, *dbd = nullptr;
+    BestDev d = g_held.D[(size_t)k]; d.q = nullptr; d.q_out = nullptr; d.skip = nullptr;      // the held key frame, this call's points
+    BestParams hB; BestParams* dB = nullptr; int* dpref = nullptr;
+    const int pref[2] = {0, (np + 3) / 4};
     const orbhip_projection hP = bare_projection(*proj);
     const hipError_t e = arena_call(device, ts, [&](Arena& A) {
-        A.io(&dqd, (size_t)np * 32, point_desc, (size_t)np * 32); A.io(&dpts, np, points, np); A.io(&dP, 1, &hP, 1);
-        A.io(&dbi, np, (const int*)nullptr, 0, best_idx, np); A.io(&dbd, np, (const int*)nullptr, 0, best_dist, np);
-    }, [&] {
-        BestParams B = g_held.B[(size_t)k];
-        B.q = nullptr; B.qdesc = dqd; B.nq = np; B.chi2_gate = chi2_gate; B.pts = dpts; B.proj = dP; B.q_out = nullptr; B.best_idx = dbi; B.best_dist = dbd; B.skip = nullptr; B.skip_bit = 0;
-        orbhip_launch_best_in_window(B, ts, fp_contract_of(proj));
-    }, g_held.floor);
+        A.io(&dB, 1, (const BestParams*)&hB, 1); A.io(&dpref, 2, pref, 2);
+        arena_in(A, &d.qdesc, point_desc, (size_t)np * 32); arena_in(A, &d.pts, points, (size_t)np); arena_in(A, &d.proj, &hP, 1);
+        A.io(&d.best_idx, (size_t)np, (const int*)nullptr, 0, best_idx, (size_t)np); A.io(&d.best_dist, (size_t)np, (const int*)nullptr, 0, best_dist, (size_t)np);
+        hB = best_block(d, g_held.bounds[(size_t)k], np, chi2_gate, 0);
+    }, [&] { orbhip_launch_best_in_window(dB, dpref, 1, pref[1], ts, fp_contract_of(proj)); }, g_held.floor);
     if (e == hipErrorOutOfMemory) return fail(ORBHIP_ERR_INVALID, "the held scratch has no room for %d points", np);      // (the caller falls back to the full entry)
     if (e != hipSuccess) { no_match(best_idx, best_dist, np); return fail(ORBHIP_ERR_HIP, "project_best_in_window_held: %s", hipGetErrorString(e)); }
     return ORBHIP_OK;
@@ -433,29 +443,29 @@ extern "C" orbhip_status orbhip_search_best_in_window_batch(int device, int nslo
     for (int s = 0; s < nslots; s++) {
         const orbhip_best_slot& S = slots[s];
         if (S.nq > 0 && !S.queries) return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
-        in[s] = BestSlotIn{S.kps, S.desc, S.u_right, S.n, S.bounds, S.inv_level_sigma2, S.nlevels, S.queries, S.query_desc, S.nq, nullptr, nullptr, S.best_idx, S.best_dist};
+        in[s] = BestSlotIn{SearchFrame{device, nullptr, S.n, S.bounds, true, S.kps, S.desc, S.u_right}, S.inv_level_sigma2, S.nlevels, S.queries, S.query_desc, S.nq, nullptr, nullptr, nullptr, S.best_idx, S.best_dist};
     }
-    return search_best_in_window_batch_impl(device, nslots, in.data(), chi2_gate);
+    return search_best_in_window_slots(device, nslots, in.data(), chi2_gate, BATCH, nullptr);
 }
 // orbhip_project_best_in_window_batch / _shared: the slots' points projected on the device
-static orbhip_status project_best_in_window_slots(int device, int nslots, const orbhip_project_best_slot* slots, int chi2_gate, bool shared, const uint64_t* skip)
+static orbhip_status project_best_in_window_slots(int device, int nslots, const orbhip_project_best_slot* slots, int chi2_gate, SlotForm form, const uint64_t* skip)
 {
     if (nslots < 0 || (nslots > 0 && !slots)) return fail(ORBHIP_ERR_INVALID, "bad argument");
     std::vector<BestSlotIn> in((size_t)nslots);
     for (int s = 0; s < nslots; s++) {
         const orbhip_project_best_slot& S = slots[s];
         if (S.np > 0 && (!S.points || !S.proj)) return fail(ORBHIP_ERR_INVALID, "bad argument in slot %d", s);
-        in[s] = BestSlotIn{S.kps, S.desc, S.u_right, S.n, S.bounds, S.inv_level_sigma2, S.nlevels, nullptr, S.point_desc, S.np, S.np > 0 ? S.proj : nullptr, S.np > 0 ? S.points : nullptr, S.best_idx, S.best_dist};
+        in[s] = BestSlotIn{SearchFrame{device, nullptr, S.n, S.bounds, true, S.kps, S.desc, S.u_right}, S.inv_level_sigma2, S.nlevels, nullptr, S.point_desc, S.np, S.np > 0 ? S.proj : nullptr, S.np > 0 ? S.points : nullptr, nullptr, S.best_idx, S.best_dist};
     }
-    return search_best_in_window_batch_impl(device, nslots, in.data(), chi2_gate, shared, skip);
+    return search_best_in_window_slots(device, nslots, in.data(), chi2_gate, form, skip);
 }
 extern "C" orbhip_status orbhip_project_best_in_window_batch(int device, int nslots, orbhip_project_best_slot* slots, int chi2_gate)
 {
-    return project_best_in_window_slots(device, nslots, slots, chi2_gate, false, nullptr);
+    return project_best_in_window_slots(device, nslots, slots, chi2_gate, BATCH, nullptr);
 }
 extern "C" orbhip_status orbhip_project_best_in_window_shared(int device, int nslots, orbhip_project_best_slot* slots, const uint64_t* skip, int chi2_gate)
 {
-    return project_best_in_window_slots(device, nslots, slots, chi2_gate, true, skip);
+    return project_best_in_window_slots(device, nslots, slots, chi2_gate, SHARED, skip);
 }
 
 // ---------------------------------------------------------------------------------------------- stateless matcher entry points
