@@ -6,6 +6,8 @@
 //   transform(features, BowVector&, FeatureVector&, levelsup) Frame.cc:400, KeyFrame.cc:50 (levelsup = 4)
 //   score(BowVector, BowVector)                               KeyFrameDatabase.cc:133,249, LoopClosing.cc:134
 //   size(), empty()
+//   create(training_features, k, L, weighting, scoring)      TemplatedVocabulary.h:604-616: hierarchical k-means on the device
+//   saveToTextFile(filename)                                  TemplatedVocabulary.h:1429-1449, byte for byte
 // plus ComputeBoW(extractor, ...) which transforms the descriptors of the extractor's last frame where they lie in HBM
 // (Frame::ComputeBoW, Frame.cc:395-402, without the host round trip).
 //
@@ -43,6 +45,8 @@ namespace DBoW2 {
 typedef unsigned int WordId;
 typedef double WordValue;
 typedef unsigned int NodeId;
+enum WeightingType { TF_IDF, TF, IDF, BINARY };                                        // BowVector.h:36-53
+enum ScoringType { L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT };
 class BowVector : public std::map<WordId, WordValue> {};
 class FeatureVector : public std::map<NodeId, std::vector<unsigned int> > {};
 }  // namespace DBoW2
@@ -63,6 +67,17 @@ public:
 
     // Loads the vocabulary from a text file (k L scoring weighting / parent isLeaf 32 bytes weight per node)
     bool loadFromTextFile(const std::string &filename);
+
+    // Builds the vocabulary from training features (one vector of 1x32 CV_8U descriptors per image; an image without features still counts as a document).
+    // Like the reference, the k-means means are written INTO the training features that seeded their clusters: the caller's Mats are modified.
+    // Unlike the reference, which draws from rand() seeded by the clock, the result is a function of the input and SetTrainingSeed's value.
+    // Throws ORBhipError (k outside 2..32, L outside 1..10, a cluster that loses all its features - where the reference crashes).
+    void create(const std::vector<std::vector<cv::Mat> > &training_features, int k, int L,
+                DBoW2::WeightingType weighting = DBoW2::TF_IDF, DBoW2::ScoringType scoring = DBoW2::L1_NORM);
+    void SetTrainingSeed(unsigned int seed) { mnTrainingSeed = seed; }
+
+    // Saves the vocabulary in the text format loadFromTextFile reads
+    void saveToTextFile(const std::string &filename) const;
 
     // Number of words; whether the vocabulary is empty
     unsigned int size() const;
@@ -89,6 +104,7 @@ private:
 
     orbhip_voc* mpVoc;
     int mnDevice;
+    unsigned int mnTrainingSeed;
 };
 
 } //namespace ORB_SLAM

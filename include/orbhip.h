@@ -348,6 +348,23 @@ orbhip_status orbhip_voc_load_text(orbhip_voc** out, const char* path, int devic
 void orbhip_voc_destroy(orbhip_voc* voc);
 /* m_k, m_L, m_scoring, m_weighting, m_nodes.size(), size() */
 orbhip_status orbhip_voc_info(const orbhip_voc* voc, int* k, int* L, int* scoring, int* weighting, int* nnodes, int* nwords);
+/* TemplatedVocabulary::create (TemplatedVocabulary.h:558-616, :642-996) on the device: hierarchical k-means++ / k-medians over 256-bit descriptors,
+   every node of a level at once, then the words' weights.  desc: the training features, image after image (image_counts[i] of image i, nimages images;
+   an image without features still counts as a document).  weighting 0..3 = TF_IDF, TF, IDF, BINARY; scoring 0..5 as in a vocabulary file.
+   The reference draws from rand() in depth-first order, seeded from the clock; here every node that runs k-means reseeds glibc's stream (restated)
+   with (seed ^ first * 0x9E3779B1 ^ n * 0x85EBCA6B) & 0x7fffffff, first = the node's first feature in training order, n = its feature count: with that rule
+   driven into the reference's own code (a subclass overriding initiateClusters), node ids, word ids, descriptors and weights are the reference's, bit for bit.
+   The reference's centres alias training features and its means overwrite them: desc_after (may be NULL, n x 32) receives the features as create() leaves them,
+   word_docs (may be NULL, one per word) the number of training images that reach each word.
+   Envelope: k 2..32, L 1..10, at most 2^31 / 32 features (about 120 bytes of device memory per feature).  A cluster that loses all its features (the reference
+   dereferences a null pointer there) and a level whose k-means has not settled after 512 passes (the reference would loop on) are ORBHIP_ERR_UNSUPPORTED
+   naming the node; nothing is returned and the library stays usable. */
+orbhip_status orbhip_voc_create(orbhip_voc** out, int device, const uint8_t* desc, const int32_t* image_counts, int nimages, int k, int L,
+                                int weighting, int scoring, uint32_t seed, uint8_t* desc_after, int32_t* word_docs);
+/* TemplatedVocabulary::saveToTextFile (:1429-1449), byte for byte; of a created or a loaded vocabulary */
+orbhip_status orbhip_voc_save_text(const orbhip_voc* voc, const char* path);
+/* the last orbhip_voc_create of the calling thread: milliseconds of device work per level 1..L (k-means) and at [0] the weights' pass; returns the levels run */
+int orbhip_voc_create_level_ms(double* ms, int cap);
 /* transform(feature, word_id, weight, nid, levelsup) for n features (TemplatedVocabulary.h:1218-1262); outputs may be NULL */
 orbhip_status orbhip_voc_transform_features(orbhip_voc* voc, const uint8_t* desc /* n x 32 */, int n, int levelsup,
                                             uint32_t* word, double* weight, uint32_t* node);

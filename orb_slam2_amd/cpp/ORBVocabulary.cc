@@ -12,7 +12,7 @@
 namespace ORB_SLAM2
 {
 
-ORBVocabulary::ORBVocabulary() : mpVoc(NULL), mnDevice(0)
+ORBVocabulary::ORBVocabulary() : mpVoc(NULL), mnDevice(0), mnTrainingSeed(0)
 {
     if (const char* dev = getenv("ORBHIP_DEVICE")) mnDevice = atoi(dev);
 }
@@ -28,6 +28,35 @@ bool ORBVocabulary::loadFromTextFile(const std::string &filename)
         return false;
     }
     return true;
+}
+
+void ORBVocabulary::create(const std::vector<std::vector<cv::Mat> > &training_features, int k, int L, DBoW2::WeightingType weighting, DBoW2::ScoringType scoring)
+{
+    std::vector<int> counts(training_features.size());
+    size_t total = 0;
+    for (size_t i = 0; i < training_features.size(); i++) { counts[i] = (int)training_features[i].size(); total += training_features[i].size(); }
+    std::vector<unsigned char> desc(total * 32 + 1), after(total * 32 + 1);
+    size_t at = 0;
+    for (size_t i = 0; i < training_features.size(); i++)
+        for (size_t j = 0; j < training_features[i].size(); j++, at++) {
+            const cv::Mat& f = training_features[i][j];
+            if (f.rows * f.cols != 32 || !f.data) throw ORBhipError("ORBVocabulary::create: a training feature is not a 1x32 CV_8U descriptor");
+            memcpy(&desc[at * 32], f.data, 32);
+        }
+    orbhip_voc* made = NULL;
+    if (orbhip_voc_create(&made, mnDevice, &desc[0], counts.empty() ? NULL : &counts[0], (int)counts.size(), k, L, (int)weighting, (int)scoring, mnTrainingSeed, &after[0], NULL) != ORBHIP_OK)
+        throw ORBhipError(std::string("ORBVocabulary::create: ") + orbhip_last_error());      // the vocabulary held before stays
+    if (mpVoc) orbhip_voc_destroy(mpVoc);
+    mpVoc = made;
+    at = 0;                                                          // the reference's centres alias the training features: what it leaves in them
+    for (size_t i = 0; i < training_features.size(); i++)
+        for (size_t j = 0; j < training_features[i].size(); j++, at++) memcpy(training_features[i][j].data, &after[at * 32], 32);
+}
+
+void ORBVocabulary::saveToTextFile(const std::string &filename) const
+{
+    if (!mpVoc) throw ORBhipError("ORBVocabulary::saveToTextFile: no vocabulary");
+    if (orbhip_voc_save_text(mpVoc, filename.c_str()) != ORBHIP_OK) throw ORBhipError(std::string("ORBVocabulary::saveToTextFile: ") + orbhip_last_error());
 }
 
 unsigned int ORBVocabulary::size() const

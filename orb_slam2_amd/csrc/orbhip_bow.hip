@@ -837,9 +837,21 @@ extern "C" orbhip_status orbhip_voc_load_text(orbhip_voc** out, const char* path
         weight.push_back(strtod(p, &e));
         word.push_back(leaf > 0 ? nwords++ : -1);
     }
-    const int nn = (int)parent.size();
+    std::vector<uint8_t> leaf(parent.size());
+    for (size_t i = 0; i < leaf.size(); i++) leaf[i] = word[i] >= 0;
+    return orbhip_voc_from_tree(out, device, k, L, n1, n2, (int)parent.size(), parent.data(), leaf.data(), desc.data(), weight.data());
+}
+
+// A vocabulary from its tree in node-id order (parents precede their children, node 0 is the root; leaves become words in id order, :918-938): what the
+// text loader and orbhip_voc_create (orbhip_voc_train.hip) both end in.
+orbhip_status orbhip_voc_from_tree(orbhip_voc** out, int device, int k, int L, int scoring, int weighting, int nn, const int* parent, const uint8_t* leaf, const uint8_t* desc, const double* weight)
+{
+    *out = nullptr;
+    std::vector<int> nchild(nn, 0), word(nn, -1);
+    int nwords = 0;
+    for (int i = 1; i < nn; i++) { nchild[parent[i]]++; word[i] = leaf[i] ? nwords++ : -1; }
     orbhip_voc* v = new orbhip_voc();
-    v->k = k; v->L = L; v->scoring = n1; v->weighting = n2; v->nnodes = nn; v->nwords = nwords; v->device = device;
+    v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting; v->nnodes = nn; v->nwords = nwords; v->device = device;
     std::vector<int> child_start(nn + 1, 0), child_ids(std::max(nn - 1, 1), 0);
     for (int i = 0; i < nn; i++) child_start[i + 1] = child_start[i] + nchild[i];
     { std::vector<int> fill(child_start.begin(), child_start.end() - 1); for (int i = 1; i < nn; i++) child_ids[fill[parent[i]]++] = i; }   // children in file order
@@ -865,6 +877,49 @@ extern "C" orbhip_status orbhip_voc_load_text(orbhip_voc** out, const char* path
     if (e != hipSuccess) { orbhip_voc_destroy(v); return orbhip_set_error(ORBHIP_ERR_HIP, "vocabulary upload failed: %s", hipGetErrorString(e)); }
     { std::lock_guard<std::mutex> all(g_vocs_m); g_vocs.push_back(v); }
     *out = v;
+    return ORBHIP_OK;
+}
+
+// The word every one of n descriptors that lie in device memory walks to (k_bow_descend), left in device memory: orbhip_voc_create counts the training
+// images of a word from it.  d_weight / d_node: n entries of scratch.  Asynchronous on s.
+orbhip_status orbhip_voc_words_resident(orbhip_voc* v, const uint8_t* d_desc, int n, uint32_t* d_word, double* d_weight, uint32_t* d_node, hipStream_t s)
+{
+    if (n <= 0 || v->nwords == 0) return ORBHIP_OK;
+    BowParams P; memset(&P, 0, sizeof P);
+    P.desc = d_desc; P.nfeat_fixed = n; P.cap = n; P.lcap = n; P.nodes = v->d_nodes; P.L = v->L; P.levelsup = 0;
+    P.word = d_word; P.weight = d_weight; P.node = d_node;
+    hipLaunchKernelGGL(k_bow_descend, dim3((n + 64 / BD_G - 1) / (64 / BD_G), 1, 1), dim3(64, 1, 1), 0, s, P);
+    BOWCHK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+// TemplatedVocabulary::saveToTextFile (:1429-1449): "k L  scoring weighting" (two spaces: the reference streams " " twice), then per node in id order
+// "parent leaf b0 b1 ... b31  weight" - FORB::toString ends every byte with a space (FORB.cpp:105-116) and one more precedes the weight, which an
+// ostream prints as %g.  The tree is read back from the device, so a loaded vocabulary saves as well as a created one.
+extern "C" orbhip_status orbhip_voc_save_text(const orbhip_voc* v, const char* path)
+{
+    if (!v || !path) return orbhip_set_error(ORBHIP_ERR_INVALID, "null argument");
+    std::vector<BowNode> nodes(v->nnodes);
+    BOWCHK(hipSetDevice(v->device));
+    BOWCHK(hipMemcpy(nodes.data(), v->d_nodes, (size_t)v->nnodes * sizeof(BowNode), hipMemcpyDeviceToHost));
+    std::vector<int> at(v->nnodes, 0), parent(v->nnodes, 0);                              // where node id lies in the breadth-first table; its parent's id
+    for (int q = 0; q < v->nnodes; q++) {
+        const BowNode& r = nodes[q];
+        if (r.id >= (uint32_t)v->nnodes || (size_t)r.first_child + r.nchildren > (size_t)v->nnodes) return orbhip_set_error(ORBHIP_ERR_HIP, "vocabulary table damaged at record %d", q);
+        at[r.id] = q;
+        for (uint32_t c = 0; c < r.nchildren; c++) parent[nodes[r.first_child + c].id] = (int)r.id;
+    }
+    FILE* f = fopen(path, "w");
+    if (!f) return orbhip_set_error(ORBHIP_ERR_INVALID, "cannot write vocabulary file %s", path);
+    fprintf(f, "%d %d  %d %d\n", v->k, v->L, v->scoring, v->weighting);
+    for (int id = 1; id < v->nnodes; id++) {
+        const BowNode& r = nodes[at[id]];
+        uint8_t d[32]; memcpy(d, &r.da, 16); memcpy(d + 16, &r.db, 16);
+        fprintf(f, "%d %d ", parent[id], r.nchildren == 0 ? 1 : 0);
+        for (int i = 0; i < 32; i++) fprintf(f, "%d ", (int)d[i]);
+        fprintf(f, " %g\n", r.weight);
+    }
+    if (fclose(f) != 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "writing vocabulary file %s failed", path);
     return ORBHIP_OK;
 }
 

@@ -221,6 +221,9 @@ void orbhip_launch_match_select(const MatchParams& M, int nslots, hipStream_t s)
 // shared with orbhip_bow.hip
 // the BowVector orbhip_compute_bow left in HBM for `frame` of ctx's last call (orbhip_kfdb_query_frame reads it in place): ids, weights, the count, the arrays' capacity
 orbhip_status orbhip_bow_resident(orbhip_ctx* ctx, orbhip_voc* voc, int frame, const uint32_t** d_id, const double** d_val, const int** d_nbow, int* cap, int* device, int* nwords, hipStream_t* s);
+// a vocabulary from its tree in node-id order (desc: nn x 32, weight: nn; leaf[i] != 0: node i is a word); the words of n device-resident descriptors (orbhip_voc_train.hip)
+orbhip_status orbhip_voc_from_tree(orbhip_voc** out, int device, int k, int L, int scoring, int weighting, int nn, const int* parent, const uint8_t* leaf, const uint8_t* desc, const double* weight);
+orbhip_status orbhip_voc_words_resident(orbhip_voc* v, const uint8_t* d_desc, int n, uint32_t* d_word, double* d_weight, uint32_t* d_node, hipStream_t s);
 void orbhip_bow_forget_ctx(const orbhip_ctx* ctx);      // frees the per-context BoW workspaces every live vocabulary keeps for ctx (called by orbhip_destroy)
 // v_writelane_b32: a wave-uniform value dropped into ONE lane of a register (lane index wave-uniform too).  The compiler has no builtin for
 // it, so the device pass spells the instruction; every other pass (hipcc's host pass, the test emulation) sees the plain selection.

@@ -42,6 +42,7 @@ SYMBOLS = [
     "orbhip_predict_scale_table", "orbhip_project_search_bounds", "orbhip_project_search_frame", "orbhip_project_best_in_window_bounds", "orbhip_project_best_in_window_batch", "orbhip_project_best_in_window_shared", "orbhip_project_best_in_window_held",
     "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_clear", "orbhip_kfdb_size", "orbhip_kfdb_add", "orbhip_kfdb_erase", "orbhip_kfdb_query", "orbhip_kfdb_query_frame",
     "orbhip_kfdb_state", "orbhip_kfdb_scores", "orbhip_kfdb_select",
+    "orbhip_voc_create", "orbhip_voc_save_text", "orbhip_voc_create_level_ms",
 ]
 
 
@@ -145,6 +146,9 @@ def lib(path=None):
     L.orbhip_extract_device_color.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]
     L.orbhip_voc_load_text.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int]
     L.orbhip_voc_destroy.argtypes = [vp]
+    L.orbhip_voc_create.argtypes = [C.POINTER(vp), C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, vp, vp]
+    L.orbhip_voc_save_text.argtypes = [vp, C.c_char_p]
+    L.orbhip_voc_create_level_ms.argtypes = [vp, C.c_int]
     L.orbhip_voc_destroy.restype = None
     L.orbhip_voc_info.argtypes = [vp, ip, ip, ip, ip, ip, ip]
     L.orbhip_voc_transform_features.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
@@ -261,7 +265,9 @@ OK, ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_UNSUPPORTED = 0, 1, 2, 3, 4      # o
 
 def _check(st, what, L=None):
     if st != 0:
-        raise OrbHipError(f"{what} failed (status {st}): {(L or lib()).orbhip_last_error().decode()}")
+        e = OrbHipError(f"{what} failed (status {st}): {(L or lib()).orbhip_last_error().decode()}")
+        e.status = st
+        raise e
 
 
 class ORBextractor:
@@ -965,6 +971,39 @@ class ORBVocabulary:
         _check(self.L_.orbhip_voc_info(self.h, *[C.byref(x) for x in v]), "orbhip_voc_info", self.L_)
         self.k, self.L, self.scoring, self.weighting, self.nnodes, self.nwords = [x.value for x in v]
         return True
+
+    def _info(self):
+        v = [C.c_int() for _ in range(6)]
+        _check(self.L_.orbhip_voc_info(self.h, *[C.byref(x) for x in v]), "orbhip_voc_info", self.L_)
+        self.k, self.L, self.scoring, self.weighting, self.nnodes, self.nwords = [x.value for x in v]
+
+    @classmethod
+    def create(cls, features_per_image, k, L, weighting=0, scoring=0, seed=0, return_features=False, device=0, library=None):
+        """TemplatedVocabulary::create (TemplatedVocabulary.h:558-616) on the device: features_per_image = one (n_i x 32) uint8 array per training image
+        (n_i may be 0), weighting 0..3 = TF_IDF, TF, IDF, BINARY, scoring 0..5 as in a vocabulary file, seed = the base of the per-node random streams
+        (DESIGN.md H14).  Returns the vocabulary, whose word_docs holds the number of training images that reach each word; with return_features also the
+        features as create() leaves them (the reference writes cluster means into the training features), one array per image."""
+        v = cls(None, device, library)
+        imgs = [np.ascontiguousarray(f, np.uint8).reshape(-1, 32) for f in features_per_image]
+        counts = np.array([len(f) for f in imgs], np.int32)
+        desc = np.ascontiguousarray(np.concatenate(imgs)) if len(imgs) and counts.sum() else np.zeros((0, 32), np.uint8)
+        after = np.zeros_like(desc)
+        docs = np.zeros(max(len(desc) + 1, 1), np.int32)                      # (a vocabulary has at most one word per feature)
+        _check(v.L_.orbhip_voc_create(C.byref(v.h), device, _p(desc), _p(counts), len(counts), k, L, weighting, scoring, seed & 0xffffffff, _p(after), _p(docs)),
+               "orbhip_voc_create", v.L_)
+        v._info()
+        v.word_docs = docs[:v.nwords].copy()
+        ms = np.zeros(16, np.float64)
+        nl = v.L_.orbhip_voc_create_level_ms(_p(ms), 16)
+        v.weights_ms, v.level_ms = float(ms[0]), ms[1:nl + 1].copy()
+        if not return_features:
+            return v
+        off = np.concatenate([[0], np.cumsum(counts)])
+        return v, [after[off[i]:off[i + 1]] for i in range(len(counts))]
+
+    def saveToTextFile(self, path):
+        """TemplatedVocabulary::saveToTextFile (:1429-1449), byte for byte"""
+        _check(self.L_.orbhip_voc_save_text(self.h, str(path).encode()), "orbhip_voc_save_text", self.L_)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
