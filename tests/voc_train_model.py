@@ -17,6 +17,17 @@ import numpy as np
 
 POP = np.array([bin(i).count("1") for i in range(256)], np.int64)
 MAX_PASSES = 512                       # the product's bound on the Lloyd passes of a level
+CHUNK = 1024                           # the product's VT_CHUNK: a node of more features is cut into several chunks and takes the device-memory counter path
+
+
+# train()'s counters.  Per k-means node: early_stop (k-means++ ran out of distance before k centres), singleton (a cluster of exactly one feature ends its
+# centre's alias), one_centre (the node keeps a single centre), each also counted as big_* when the node has more than CHUNK features; zero_cut (a cut of 0.0
+# drawn again, TemplatedVocabulary.h:887-891); key_zero (the node's srand key is 0).  Per call: alias_write, passes (the most Lloyd passes of a node),
+# leaf_above_L, zero_docs (words no walk reaches), empty_images, empty_run (the longest run of consecutive empty images), max_level_nodes (the most k-means
+# nodes on one level), kmeans_levels (levels with at least one k-means node: what orbhip_voc_create_level_ms counts), settles_past_512 (levels on which a
+# k-means node past the first 512 takes more Lloyd passes than every one of the first 512: the level's passes end with a node of the third workgroup).
+STAT_KEYS = ("early_stop", "singleton", "alias_write", "passes", "leaf_above_L", "zero_docs", "empty_images", "big_early_stop", "big_singleton", "one_centre",
+             "big_one_centre", "zero_cut", "key_zero", "max_level_nodes", "empty_run", "kmeans_levels", "settles_past_512")
 
 
 class EmptyCluster(Exception):
@@ -61,9 +72,12 @@ def mean_value(rows):
 
 
 def _kmeans(feats, idx, k, base, stats):
-    """HKmeansStep's k-means on the node whose features are idx (:671-783) -> (centres: feature slot or -1, own buffers, association)"""
+    """HKmeansStep's k-means on the node whose features are idx (:671-783) -> (centres: feature slot or -1, own buffers, association, Lloyd passes)"""
     n = len(idx)
-    rng = Rand(seed_of(base, int(idx[0]), n))
+    big = n > CHUNK
+    key = seed_of(base, int(idx[0]), n)
+    stats["key_zero"] += key == 0
+    rng = Rand(key)
     slots = [int(idx[int((rng() / 2147483648.0) * n)])]
     d = feats[idx]
     mind = ham(d, feats[slots[0]])
@@ -73,15 +87,17 @@ def _kmeans(feats, idx, k, base, stats):
         mind[m] = nd[m]
         s = int(mind.sum())
         if s == 0:
-            stats["early_stop"] += 1
+            stats["early_stop"] += 1; stats["big_early_stop"] += big
             break
         while True:
             cut = (rng() / 2147483647.0) * s
             if cut != 0.0:
                 break
+            stats["zero_cut"] += 1
         j = int(np.searchsorted(np.cumsum(mind), cut, side="left"))
         slots.append(int(idx[min(j, n - 1)]))
     nc = len(slots)
+    stats["one_centre"] += nc == 1; stats["big_one_centre"] += big and nc == 1
     own = [None] * nc
     assoc = last = None
     for npass in range(MAX_PASSES + 1):
@@ -92,7 +108,7 @@ def _kmeans(feats, idx, k, base, stats):
                     raise EmptyCluster(f"node of {n} features from feature {int(idx[0])}: cluster {c} is empty in pass {npass}")
                 if len(members) == 1:
                     if slots[c] >= 0:
-                        stats["singleton"] += 1
+                        stats["singleton"] += 1; stats["big_singleton"] += big
                     own[c] = feats[members[0]].copy(); slots[c] = -1
                 else:
                     mean = mean_value(feats[members])
@@ -109,7 +125,7 @@ def _kmeans(feats, idx, k, base, stats):
         last, assoc = assoc, np.argmin(dist, axis=0)                          # the first of equal minima
         if last is not None and np.array_equal(last, assoc):
             stats["passes"] = max(stats["passes"], npass)
-            return slots, own, assoc
+            return slots, own, assoc, npass
     raise RuntimeError("k-means did not settle")
 
 
@@ -118,7 +134,9 @@ def train(images, k, L, weighting=0, scoring=0, seed=0):
     counts = [len(f) for f in images]
     feats = np.concatenate([np.asarray(f, np.uint8).reshape(-1, 32) for f in images]).copy() if sum(counts) else np.zeros((0, 32), np.uint8)
     M = len(feats)
-    stats = dict(early_stop=0, singleton=0, alias_write=0, passes=0, leaf_above_L=0, zero_docs=0, empty_images=sum(c == 0 for c in counts))
+    stats = dict.fromkeys(STAT_KEYS, 0)
+    stats["empty_images"] = sum(c == 0 for c in counts)
+    stats["empty_run"] = max((len(r) for r in "".join("e" if c == 0 else " " for c in counts).split()), default=0)
     hparent, hslot, hown, hkids, hlevel = [0], [-1], [None], [[]], [0]
 
     def add(p, slot, own, level):
@@ -129,17 +147,22 @@ def train(images, k, L, weighting=0, scoring=0, seed=0):
     work = [(0, np.arange(M))] if M else []
     for level in range(1, L + 1):
         nxt = []
+        width = sum(len(idx) > k for _, idx in work)
+        stats["max_level_nodes"] = max(stats["max_level_nodes"], width); stats["kmeans_levels"] += width > 0
+        passes = []                                                           # of this level's k-means nodes, in the product's node order
         for h, idx in work:
             if len(idx) <= k:                                                 # :660-670
                 for f in idx:
                     add(h, int(f), None, level)
                 continue
-            slots, own, assoc = _kmeans(feats, idx, k, seed, stats)
+            slots, own, assoc, npass = _kmeans(feats, idx, k, seed, stats)
+            passes.append(npass)
             for c in range(len(slots)):
                 child = add(h, slots[c], own[c], level)
                 g = idx[assoc == c]
                 if len(g) > 1 and level < L:
                     nxt.append((child, g))
+        stats["settles_past_512"] += len(passes) > 512 and max(passes[512:]) > max(passes[:512])
         work = nxt
     # ids: a node's children take the next ids when it is visited, then the children are visited in order (:786-817)
     nn = len(hparent)
@@ -234,6 +257,16 @@ def few_values(seed, counts, nvalues):
     return [desc[off[i]:off[i + 1]] for i in range(len(counts))]
 
 
+def counted_values(seed, counts_per_value, image_counts):
+    """one random value per entry of `counts_per_value`, each taken by exactly that many features, in shuffled order"""
+    rng = np.random.default_rng(seed)
+    vals = rng.integers(0, 256, (len(counts_per_value), 32), dtype=np.uint8)
+    assert len(np.unique(vals, axis=0)) == len(vals) and sum(counts_per_value) == sum(image_counts)
+    desc = vals[rng.permutation(np.repeat(np.arange(len(vals)), counts_per_value))]
+    off = np.concatenate([[0], np.cumsum(image_counts)])
+    return [desc[off[i]:off[i + 1]] for i in range(len(image_counts))]
+
+
 def split(total, nimages, seed, empty=()):
     """`total` features over `nimages` images, those listed in `empty` without any"""
     rng = np.random.default_rng(seed)
@@ -266,8 +299,38 @@ for _m in ROOT_SIZES:
     CASES["root_%d" % _m] = (10, 1, 0, 0, 20 + _m, (lambda m: lambda: make_set(200 + m, split(m, 3, m)))(_m))
 
 
+# Node shapes and draws the cases above do not reach (tests/golden/voc_train_shapes_ref.npz).  The root of a set of n features starts at feature 0, so its
+# srand key is (base ^ n * 0x85EBCA6B) & 0x7fffffff: root_key(n, s) is the base seed that makes it s.  srand(1866778841) returns 0 at draw 1 and
+# srand(1974820829) at draw 3 (draw 0 picks the first centre); both bases come out above 2^31.
+def root_key(n, s):
+    return (s ^ (n * 0x85EBCA6B)) & 0xffffffff
+
+
+SHAPES = {
+    "big_few_values": (5, 3, 0, 0, 31, lambda: counted_values(301, (1300, 700, 1), split(2001, 6, 31))),
+    "zero_cut_first": (10, 1, 0, 0, root_key(300, 1866778841), lambda: make_set(303, split(300, 4, 33), 25, 0.2)),
+    "zero_cut_later": (10, 1, 0, 0, root_key(300, 1974820829), lambda: make_set(303, split(300, 4, 33), 25, 0.2)),
+    "root_key_zero": (10, 2, 0, 0, root_key(300, 0), lambda: make_set(304, split(300, 4, 34), 25, 0.2)),
+    "wide_level": (3, 7, 0, 0, 47, lambda: make_set(302, split(6000, 9, 32))),
+    "one_image": (6, 3, 0, 0, 35, lambda: make_set(305, [400], 30, 0.2)),
+    "empty_runs": (6, 2, 0, 0, 36, lambda: make_set(306, [0, 0, 1, 150, 0, 0, 0, 1, 148, 0, 0], 12, 0.15)),
+}
+for _m in (2048, 2049):
+    SHAPES["root_%d" % _m] = (10, 1, 0, 0, 20 + _m, (lambda m: lambda: make_set(200 + m, split(m, 3, m)))(_m))
+# what each case was made for: the least its counter must say (train()["stats"], stored beside the golden)
+REACHES = {
+    "big_few_values": dict(big_early_stop=3, big_singleton=1, big_one_centre=2, one_centre=4),
+    "zero_cut_first": dict(zero_cut=1),
+    "zero_cut_later": dict(zero_cut=1),
+    "root_key_zero": dict(key_zero=1),
+    "wide_level": dict(max_level_nodes=513, settles_past_512=1),
+    "empty_runs": dict(empty_run=3, empty_images=7),
+}
+ALL = dict(CASES, **SHAPES)
+
+
 def case_images(name):
-    return CASES[name][5]()
+    return ALL[name][5]()
 
 
 def input_hash(images):
