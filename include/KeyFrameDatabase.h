@@ -2,6 +2,8 @@
 // the device key-frame database of include/orbhip.h (orbhip_kfdb_*).  The key frames' BowVectors live in device memory, one slot per key frame; this
 // class keeps the slot <-> KeyFrame* mapping.  The per-key-frame query fields (mnLoopQuery, mnLoopWords, mLoopScore, mnRelocQuery, mnRelocWords,
 // mRelocScore), which no file of ORB_SLAM2 outside KeyFrameDatabase.cc reads, live in the database and not in the KeyFrame.
+// Scores are those of the vocabulary's own scoring object (ORBVocabulary::getScoringType, read at the constructor and at every Detect as the reference
+// calls mpVoc->score there): L1_NORM, L2_NORM, CHI_SQUARE, BHATTACHARYYA or DOT_PRODUCT.  A KL vocabulary throws ORBhipError.
 #ifndef KEYFRAMEDATABASE_H
 #define KEYFRAMEDATABASE_H
 
@@ -47,11 +49,15 @@ protected:
     // one device query (kind: ORBHIP_KFDB_RELOC / ORBHIP_KFDB_LOOP), the hits' best covisibles, the covisibility selection
     std::vector<KeyFrame*> Detect(int kind, unsigned long long qid, const DBoW2::BowVector &bow, const std::set<KeyFrame*> &sConnected, float minScore);
 
+    // makes the device database score as mpVoc does now; calls the device only when that changed
+    void FollowVocabularyScoring();
+
     // Associated vocabulary
     const ORBVocabulary* mpVoc;
 
     // The device database; which key frame each of its slots holds
     orbhip_kfdb* mpDb;
+    int mnScoring;                       // what mpDb scores with (under mMutex)
     std::map<KeyFrame*, int> mSlotOf;
     std::vector<KeyFrame*> mvpKeyFrameOf;
 

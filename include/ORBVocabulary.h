@@ -8,6 +8,7 @@
 //   size(), empty()
 //   create(training_features, k, L, weighting, scoring)      TemplatedVocabulary.h:604-616: hierarchical k-means on the device
 //   saveToTextFile(filename)                                  TemplatedVocabulary.h:1429-1449, byte for byte
+//   getBranchingFactor(), getDepthLevels(), getWeightingType(), getScoringType(), setScoringType(type)   TemplatedVocabulary.h:185-235, :500-504
 // plus ComputeBoW(extractor, ...) which transforms the descriptors of the extractor's last frame where they lie in HBM
 // (Frame::ComputeBoW, Frame.cc:395-402, without the host round trip).
 //
@@ -82,6 +83,15 @@ public:
     // Number of words; whether the vocabulary is empty
     unsigned int size() const;
     bool empty() const { return size() == 0; }
+
+    // k, L, the weighting and the scoring the vocabulary was created or loaded with (0 / 0 / TF_IDF / L1_NORM while there is none)
+    int getBranchingFactor() const;
+    int getDepthLevels() const;
+    DBoW2::WeightingType getWeightingType() const;
+    DBoW2::ScoringType getScoringType() const;
+    // Changes the scoring object: score, the normalisation of every later transform and saveToTextFile's header follow.  A KeyFrameDatabase built on this
+    // vocabulary follows at its next query (it reads getScoringType there, as the reference's calls mpVoc->score).  Throws ORBhipError without a vocabulary.
+    void setScoringType(DBoW2::ScoringType type);
 
     // Transforms a set of descriptors (1x32 CV_8U each, Converter::toDescriptorVector) into a bow vector and a feature vector
     void transform(const std::vector<cv::Mat>& features, DBoW2::BowVector &v, DBoW2::FeatureVector &fv, int levelsup) const;

@@ -348,6 +348,10 @@ orbhip_status orbhip_voc_load_text(orbhip_voc** out, const char* path, int devic
 void orbhip_voc_destroy(orbhip_voc* voc);
 /* m_k, m_L, m_scoring, m_weighting, m_nodes.size(), size() */
 orbhip_status orbhip_voc_info(const orbhip_voc* voc, int* k, int* L, int* scoring, int* weighting, int* nnodes, int* nwords);
+/* TemplatedVocabulary::setScoringType (TemplatedVocabulary.h:500-504), scoring 0..5: orbhip_voc_score, the normalisation of every later transform
+   (L1 for 0, 2, 3, 4; L2 for 1; none for 5) and the header orbhip_voc_save_text writes follow.  Like the reference's, not to be called while another
+   thread uses the vocabulary. */
+orbhip_status orbhip_voc_set_scoring(orbhip_voc* voc, int scoring);
 /* TemplatedVocabulary::create (TemplatedVocabulary.h:558-616, :642-996) on the device: hierarchical k-means++ / k-medians over 256-bit descriptors,
    every node of a level at once, then the words' weights.  desc: the training features, image after image (image_counts[i] of image i, nimages images;
    an image without features still counts as a document).  weighting 0..3 = TF_IDF, TF, IDF, BINARY; scoring 0..5 as in a vocabulary file.
@@ -448,8 +452,8 @@ double orbhip_voc_score(const orbhip_voc* voc, const uint32_t* id1, const double
    The loop and relocalisation queries of ORB_SLAM2::KeyFrameDatabase on a device-resident store of the key frames' BowVectors.  A key frame is
    a SLOT (orbhip_kfdb_add hands it out, orbhip_kfdb_erase frees it for reuse); per slot and query kind the database holds what the reference
    keeps in the KeyFrame: {query, words, score} = mnRelocQuery / mnRelocWords / mRelocScore and mnLoopQuery / mnLoopWords / mLoopScore, all 0 for
-   a new key frame.  Only scoring 0 (L1_NORM, what ORBvoc.txt declares) is supported: orbhip_kfdb_create returns
-   ORBHIP_ERR_UNSUPPORTED for the others.  A BowVector has at most 8192 words, ids ascending and below nwords.  Every entry is synchronous, takes
+   a new key frame.  orbhip_kfdb_create takes scoring 0 only (L1_NORM, what ORBvoc.txt declares) and returns
+   ORBHIP_ERR_UNSUPPORTED for the others; a database is switched to the vocabulary's scoring with orbhip_kfdb_set_scoring.  A BowVector has at most 8192 words, ids ascending and below nwords.  Every entry is synchronous, takes
    host pointers, runs on the calling thread's own stream (orbhip_kfdb_query_frame: the extractor's) and holds the database's one lock, as the
    reference's members hold mMutex: add, erase and both queries may be called from different threads at once. */
 typedef struct orbhip_kfdb orbhip_kfdb;
@@ -457,6 +461,13 @@ enum { ORBHIP_KFDB_RELOC = 0, ORBHIP_KFDB_LOOP = 1 };
 typedef struct { int32_t slot; int32_t words; float score; } orbhip_kfdb_hit;     /* a scored key frame: mnRelocWords / mnLoopWords and (float)score */
 orbhip_status orbhip_kfdb_create(orbhip_kfdb** out, int device, int nwords /* ORBVocabulary::size() */, int scoring);
 void orbhip_kfdb_destroy(orbhip_kfdb* db);
+/* The scoring object (DBoW2's ScoringType, the third field of a vocabulary file's header) of every later orbhip_kfdb_query, _query_frame and _scores:
+   0 L1_NORM, 1 L2_NORM, 2 CHI_SQUARE, 4 BHATTACHARYYA, 5 DOT_PRODUCT, each bit for bit ScoringObject.cpp's (every operation rounds once).
+   3 (KL) is ORBHIP_ERR_UNSUPPORTED: it sums over words the key frame lacks, needs a log, and grows with dissimilarity; outside 0..5 is
+   ORBHIP_ERR_INVALID; both leave the scoring as it was.  The reference reads the vocabulary's scoring at query time (KeyFrameDatabase.cc:133,249), so
+   this is a property that may change between queries; scores earlier queries left in the key frames' state stay, as mRelocScore / mLoopScore do. */
+orbhip_status orbhip_kfdb_set_scoring(orbhip_kfdb* db, int scoring);
+int orbhip_kfdb_get_scoring(orbhip_kfdb* db);
 orbhip_status orbhip_kfdb_clear(orbhip_kfdb* db);                     /* every slot is freed */
 int orbhip_kfdb_size(orbhip_kfdb* db);                                /* key frames held */
 orbhip_status orbhip_kfdb_add(orbhip_kfdb* db, const uint32_t* bow_id, const double* bow_val, int nbow, int* slot);
@@ -474,7 +485,7 @@ orbhip_status orbhip_kfdb_query_frame(orbhip_kfdb* db, int kind, uint64_t qid, o
                                       const int32_t* excluded_slots, int nexcluded, float min_score,
                                       orbhip_kfdb_hit* hits, int cap, int* nhits, int* nsharing, int* min_common);
 orbhip_status orbhip_kfdb_state(orbhip_kfdb* db, int kind, int slot, uint64_t* query, int* words, float* score);
-/* mpVoc->score(bow, key frame) for n named key frames in one launch (LoopClosing.cc:123-139); scoring as L1Scoring::score, double for double */
+/* mpVoc->score(bow, key frame) for n named key frames in one launch (LoopClosing.cc:123-139); the database's scoring object, double for double */
 orbhip_status orbhip_kfdb_scores(orbhip_kfdb* db, const uint32_t* bow_id, const double* bow_val, int nbow, const int32_t* slots, int n, double* scores);
 /* The second half (:144-196 LOOP, :258-308 RELOC), host arithmetic over the state the query left: hit i's neighbours
    neigh_slot[neigh_off[i] .. neigh_off[i+1]) = GetBestCovisibilityKeyFrames(10) of its key frame (a slot that holds no key frame is skipped).

@@ -20,12 +20,26 @@ static void FlattenBow(const DBoW2::BowVector &bow, std::vector<uint32_t> &id, s
     for (DBoW2::BowVector::const_iterator it = bow.begin(); it != bow.end(); ++it) { id.push_back(it->first); val.push_back(it->second); }
 }
 
-// ORB_SLAM2's vocabularies (ORBvoc.txt) declare L1_NORM, scoring 0: the one the device database scores with
-KeyFrameDatabase::KeyFrameDatabase(const ORBVocabulary &voc) : mpVoc(&voc), mpDb(NULL)
+// A database is created scoring L1_NORM (0, what ORBvoc.txt declares) and follows the vocabulary's scoring object from there
+KeyFrameDatabase::KeyFrameDatabase(const ORBVocabulary &voc) : mpVoc(&voc), mpDb(NULL), mnScoring(0)
 {
     int device = 0;
     if (const char* dev = getenv("ORBHIP_DEVICE")) device = atoi(dev);
     orbhip_check(orbhip_kfdb_create(&mpDb, device, (int)voc.size(), 0), "KeyFrameDatabase");
+    try { FollowVocabularyScoring(); }
+    catch (...) { orbhip_kfdb_destroy(mpDb); mpDb = NULL; throw; }      // (a KL vocabulary: the destructor of a half-built object does not run)
+}
+
+void KeyFrameDatabase::FollowVocabularyScoring()
+{
+    static const char* const names[] = {"L1_NORM", "L2_NORM", "CHI_SQUARE", "KL", "BHATTACHARYYA", "DOT_PRODUCT"};
+    const int scoring = (int)mpVoc->getScoringType();
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (scoring == mnScoring) return;
+    const orbhip_status st = orbhip_kfdb_set_scoring(mpDb, scoring);
+    if (st != ORBHIP_OK)
+        throw ORBhipError(std::string("KeyFrameDatabase: the vocabulary's scoring ") + (scoring >= 0 && scoring <= 5 ? names[scoring] : "?") + ": " + orbhip_last_error());
+    mnScoring = scoring;
 }
 
 KeyFrameDatabase::~KeyFrameDatabase() { if (mpDb) orbhip_kfdb_destroy(mpDb); }
@@ -61,6 +75,7 @@ void KeyFrameDatabase::clear()
 
 std::vector<KeyFrame*> KeyFrameDatabase::Detect(int kind, unsigned long long qid, const DBoW2::BowVector &bow, const std::set<KeyFrame*> &sConnected, float minScore)
 {
+    FollowVocabularyScoring();
     std::vector<uint32_t> id; std::vector<double> val;
     FlattenBow(bow, id, val);
     std::vector<int32_t> vExcluded; int nCap = 0;

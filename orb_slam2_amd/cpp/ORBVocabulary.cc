@@ -66,6 +66,17 @@ unsigned int ORBVocabulary::size() const
     return (unsigned int)nwords;
 }
 
+int ORBVocabulary::getBranchingFactor() const { int k = 0; if (mpVoc) orbhip_voc_info(mpVoc, &k, NULL, NULL, NULL, NULL, NULL); return k; }
+int ORBVocabulary::getDepthLevels() const { int L = 0; if (mpVoc) orbhip_voc_info(mpVoc, NULL, &L, NULL, NULL, NULL, NULL); return L; }
+DBoW2::WeightingType ORBVocabulary::getWeightingType() const { int w = 0; if (mpVoc) orbhip_voc_info(mpVoc, NULL, NULL, NULL, &w, NULL, NULL); return (DBoW2::WeightingType)w; }
+DBoW2::ScoringType ORBVocabulary::getScoringType() const { int s = 0; if (mpVoc) orbhip_voc_info(mpVoc, NULL, NULL, &s, NULL, NULL, NULL); return (DBoW2::ScoringType)s; }
+
+void ORBVocabulary::setScoringType(DBoW2::ScoringType type)
+{
+    if (!mpVoc) throw ORBhipError("ORBVocabulary::setScoringType: no vocabulary");
+    if (orbhip_voc_set_scoring(mpVoc, (int)type) != ORBHIP_OK) throw ORBhipError(std::string("ORBVocabulary::setScoringType: ") + orbhip_last_error());
+}
+
 void ORBVocabulary::Deliver(int n, std::vector<unsigned int>& bowId, std::vector<double>& bowVal, int nbow, std::vector<unsigned int>& fvNode,
                             std::vector<int>& fvOff, std::vector<unsigned int>& fvFeat, int nfv, DBoW2::BowVector &v, DBoW2::FeatureVector &fv) const
 {

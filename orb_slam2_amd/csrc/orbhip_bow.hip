@@ -935,6 +935,17 @@ extern "C" orbhip_status orbhip_voc_info(const orbhip_voc* v, int* k, int* L, in
     return ORBHIP_OK;
 }
 
+// TemplatedVocabulary::setScoringType (TemplatedVocabulary.h:500-504): score, transform's normalisation and saveToTextFile's header follow.  Like the
+// reference's, not to be called while another thread transforms or scores with this vocabulary.
+extern "C" orbhip_status orbhip_voc_set_scoring(orbhip_voc* v, int scoring)
+{
+    if (!v) return orbhip_set_error(ORBHIP_ERR_INVALID, "null vocabulary");
+    if (scoring < 0 || scoring > 5) return orbhip_set_error(ORBHIP_ERR_INVALID, "vocabulary: scoring %d outside 0..5", scoring);
+    std::lock_guard<std::mutex> lock(v->m);
+    v->scoring = scoring;
+    return ORBHIP_OK;
+}
+
 static orbhip_status voc_upload(orbhip_voc* v, const uint8_t* desc, int n)
 {
     BOWCHK(hipSetDevice(v->device));

@@ -5,8 +5,9 @@
 // visited ascending, each list is in add order and erase() keeps it).  So no list exists here.  The store is a forward store: every key frame's
 // BowVector lies as one range of a word-id arena (u32) and a weight arena (f64); a query is
 //   k_kfdb_scan    one wavefront per key frame: its words are looked up in the query's sorted id list (LDS, bisection) -> shared-word count, first
-//                  shared word and the L1 score, bit for bit L1Scoring::score (ScoringObject.cpp:23-68): the terms in ascending word order in ONE
-//                  dependent f64 chain from 0
+//                  shared word and the score, bit for bit the vocabulary's scoring object (ScoringObject.cpp:23-311; L1, L2, chi-square, Bhattacharyya,
+//                  dot product: one instantiation each, orbhip_kfdb_set_scoring chooses): the terms in ascending word order in ONE dependent f64
+//                  chain from 0
 //   k_kfdb_select  one workgroup: the per-key-frame state rule of KeyFrameDatabase.cc:86-104 / :207-222 (mnRelocQuery, mnRelocWords, mRelocScore and
 //                  the mnLoop* fields live here, per slot and kind), maxCommonWords, minCommonWords = (int)(max * 0.8f), the compaction of the key frames
 //                  above it, their order (first shared word << 32 | add sequence) and the hit list (lScoreAndMatch)
@@ -47,8 +48,25 @@ __device__ __forceinline__ double kf_readlane(double v, int lane)             //
     double r; memcpy(&r, h, 8); return r;
 }
 
+// The term a shared word adds to the chain (vi the query's weight, wi the key frame's) and what becomes of the sum: SC is DBoW2's ScoringType
+// (0 L1_NORM :23-68, 1 L2_NORM :73-119, 2 CHI_SQUARE :124-188, 4 BHATTACHARYYA :243-282, 5 DOT_PRODUCT :287-311).  Every operation rounds once, to nearest.
+template <int SC> __device__ __forceinline__ double kf_term(double vi, double wi)
+{
+    if constexpr (SC == 0) return __dsub_rn(__dsub_rn(fabs(__dsub_rn(vi, wi)), fabs(vi)), fabs(wi));
+    else if constexpr (SC == 2) { const double d = __dadd_rn(vi, wi); return d != 0.0 ? __ddiv_rn(__dmul_rn(vi, wi), d) : 0.0; }      // (s + 0.0 == s: s is never -0.0)
+    else if constexpr (SC == 4) return __dsqrt_rn(__dmul_rn(vi, wi));
+    else return __dmul_rn(vi, wi);
+}
+template <int SC> __device__ __forceinline__ double kf_result(double s)
+{
+    if constexpr (SC == 0) return -s / 2.0;
+    else if constexpr (SC == 1) return s >= 1 ? 1.0 : __dsub_rn(1.0, __dsqrt_rn(__dsub_rn(1.0, s)));
+    else if constexpr (SC == 2) return __dmul_rn(2.0, s);
+    else return s;
+}
+
 #define KS_T 256                       // four wavefronts share one staged copy of the query's ids
-__global__ __launch_bounds__(KS_T) void k_kfdb_scan(KfScanParams P)
+template <int SC> __global__ __launch_bounds__(KS_T) void k_kfdb_scan(KfScanParams P)
 {
     HIP_DYNAMIC_SHARED(uint32_t, q)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -75,7 +93,7 @@ __global__ __launch_bounds__(KS_T) void k_kfdb_scan(KfScanParams P)
             double term = 0.0;
             if (hit) {                                                        // score(query, key frame): vi the query's weight, wi the key frame's; both loads leave together
                 const double wi = kval[i], vi = P.q_val[pos];
-                term = __dsub_rn(__dsub_rn(fabs(__dsub_rn(vi, wi)), fabs(vi)), fabs(wi));
+                term = kf_term<SC>(vi, wi);
             }
             unsigned long long m = __ballot(hit);
             if (m) {
@@ -86,7 +104,7 @@ __global__ __launch_bounds__(KS_T) void k_kfdb_scan(KfScanParams P)
             }
         }
     }
-    if (lane == 0) { P.cnt[w] = cnt; P.first[w] = first; P.score[w] = -s / 2.0; }
+    if (lane == 0) { P.cnt[w] = cnt; P.first[w] = first; P.score[w] = kf_result<SC>(s); }
 }
 
 // ------------------------------------------------------------------------------------------------ k_kfdb_select
@@ -206,7 +224,7 @@ __global__ __launch_bounds__(256) void k_kfdb_gather(const KfState* state, const
 
 // ------------------------------------------------------------------------------------------------ host side
 struct orbhip_kfdb {
-    int device = 0, nwords = 0;
+    int device = 0, nwords = 0, scoring = 0;                 // scoring: DBoW2's ScoringType of the next query (orbhip_kfdb_set_scoring)
     std::mutex m;
     // forward store: both arenas grow together by doubling; erased ranges are reused first-fit
     uint32_t* d_ids = nullptr; double* d_vals = nullptr; size_t arena_cap = 0, arena_end = 0;
@@ -290,6 +308,26 @@ extern "C" orbhip_status orbhip_kfdb_clear(orbhip_kfdb* db)
     return ORBHIP_OK;
 }
 
+// The scoring object of every later query: what the reference reads from the vocabulary at query time (KeyFrameDatabase.cc:133,249 call mpVoc->score).
+// Scores that earlier queries left in the key frames' state stay, as mRelocScore / mLoopScore do.
+extern "C" orbhip_status orbhip_kfdb_set_scoring(orbhip_kfdb* db, int scoring)
+{
+    if (!db) return orbhip_set_error(ORBHIP_ERR_INVALID, "null database");
+    if (scoring < 0 || scoring > 5) return orbhip_set_error(ORBHIP_ERR_INVALID, "key-frame database: scoring %d outside 0..5", scoring);
+    if (scoring == 3) return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "key-frame database: scoring 3 (KL): its sum runs over the query's words that the key frame LACKS and needs a log, "
+                                              "and as a divergence it grows with dissimilarity, so the database's higher-is-better selection means nothing under it");
+    std::lock_guard<std::mutex> lock(db->m);
+    db->scoring = scoring;
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_kfdb_get_scoring(orbhip_kfdb* db)
+{
+    if (!db) return 0;
+    std::lock_guard<std::mutex> lock(db->m);
+    return db->scoring;
+}
+
 extern "C" int orbhip_kfdb_size(orbhip_kfdb* db)
 {
     if (!db) return 0;
@@ -362,7 +400,14 @@ static void kf_launch_scan(orbhip_kfdb* db, const int* d_list, int n, const uint
     P.ids = db->d_ids; P.vals = db->d_vals; P.slots = db->d_slots; P.list = d_list; P.n = n;
     P.q_id = d_qid; P.q_val = d_qval; P.q_n_dev = d_qn; P.q_n = qn; P.q_cap = qcap;
     P.cnt = db->d_cnt; P.first = db->d_first; P.score = db->d_score;
-    hipLaunchKernelGGL(k_kfdb_scan, dim3((n + KS_T / 64 - 1) / (KS_T / 64), 1, 1), dim3(KS_T, 1, 1), (size_t)std::max(qcap, 1) * sizeof(uint32_t), s, P);
+    const dim3 g((n + KS_T / 64 - 1) / (KS_T / 64), 1, 1), b(KS_T, 1, 1); const size_t lds = (size_t)std::max(qcap, 1) * sizeof(uint32_t);
+    switch (db->scoring) {
+    case 1: hipLaunchKernelGGL(k_kfdb_scan<1>, g, b, lds, s, P); break;
+    case 2: hipLaunchKernelGGL(k_kfdb_scan<2>, g, b, lds, s, P); break;
+    case 4: hipLaunchKernelGGL(k_kfdb_scan<4>, g, b, lds, s, P); break;
+    case 5: hipLaunchKernelGGL(k_kfdb_scan<5>, g, b, lds, s, P); break;
+    default: hipLaunchKernelGGL(k_kfdb_scan<0>, g, b, lds, s, P); break;
+    }
 }
 
 // scan + select + download on stream s, the database's lock held; the query's BowVector is on the device already

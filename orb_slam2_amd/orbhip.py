@@ -41,7 +41,7 @@ SYMBOLS = [
     "orbhip_device_synchronize", "orbhip_submit_to",
     "orbhip_predict_scale_table", "orbhip_project_search_bounds", "orbhip_project_search_frame", "orbhip_project_best_in_window_bounds", "orbhip_project_best_in_window_batch", "orbhip_project_best_in_window_shared", "orbhip_project_best_in_window_held",
     "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_clear", "orbhip_kfdb_size", "orbhip_kfdb_add", "orbhip_kfdb_erase", "orbhip_kfdb_query", "orbhip_kfdb_query_frame",
-    "orbhip_kfdb_state", "orbhip_kfdb_scores", "orbhip_kfdb_select",
+    "orbhip_kfdb_state", "orbhip_kfdb_scores", "orbhip_kfdb_select", "orbhip_kfdb_set_scoring", "orbhip_kfdb_get_scoring", "orbhip_voc_set_scoring",
     "orbhip_voc_create", "orbhip_voc_save_text", "orbhip_voc_create_level_ms",
 ]
 
@@ -252,6 +252,9 @@ def lib(path=None):
     L.orbhip_kfdb_state.argtypes = [vp, C.c_int, C.c_int, u64p, ip, C.POINTER(C.c_float)]
     L.orbhip_kfdb_scores.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp]
     L.orbhip_kfdb_select.argtypes = [vp, C.c_int, C.c_uint64, C.c_int, C.c_float, vp, C.c_int, vp, vp, vp, C.c_int, ip]
+    L.orbhip_kfdb_set_scoring.argtypes = [vp, C.c_int]
+    L.orbhip_kfdb_get_scoring.argtypes = [vp]
+    L.orbhip_voc_set_scoring.argtypes = [vp, C.c_int]
     _libs[path] = L
     return L
 
@@ -1019,6 +1022,15 @@ class ORBVocabulary:
     def size(self):
         return self.nwords
 
+    def getScoringType(self):
+        return self.scoring
+
+    def setScoringType(self, scoring):
+        """TemplatedVocabulary::setScoringType (0..5 = L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT): score, the normalisation of every later
+        transform and saveToTextFile's header follow."""
+        _check(self.L_.orbhip_voc_set_scoring(self.h, int(scoring)), "orbhip_voc_set_scoring", self.L_)
+        self._info()
+
     def transform_features(self, desc, levelsup):
         desc = np.ascontiguousarray(desc, np.uint8)
         n = len(desc)
@@ -1089,6 +1101,19 @@ class KeyFrameDatabase:
 
     def __len__(self):
         return self.L_.orbhip_kfdb_size(self.h)
+
+    def set_scoring(self, scoring):
+        """The scoring object of every later query / query_frame / scores: the vocabulary's ScoringType (0 L1, 1 L2, 2 chi-square, 4 Bhattacharyya, 5 dot
+        product; 3, KL, is refused).  Scores that earlier queries left in the key frames' state stay."""
+        _check(self.L_.orbhip_kfdb_set_scoring(self.h, int(scoring)), "orbhip_kfdb_set_scoring", self.L_)
+
+    @property
+    def scoring(self):
+        return self.L_.orbhip_kfdb_get_scoring(self.h)
+
+    @scoring.setter
+    def scoring(self, scoring):
+        self.set_scoring(scoring)
 
     @staticmethod
     def _bow(bow_id, bow_val):

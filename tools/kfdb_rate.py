@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Rate of the device key-frame database (orbhip_kfdb_*): milliseconds per call and scanned bytes / time as a fraction of the HBM peak.
 
-    python tools/kfdb_rate.py [--kfs 10000] [--words 1500] [--reps 30] [--out profiles/NAME.json]
+    python tools/kfdb_rate.py [--kfs 10000] [--words 1500] [--reps 30] [--scoring 0] [--out profiles/NAME.json]
 
 Two measurements:
   query       orbhip_kfdb_query (RELOC) of a 1500-word BowVector against --kfs key frames of about --words words each, nwords = 10^6
   reloc       the full relocalisation sequence on a resident frame: compute_bow -> query_frame -> select, with the vocabulary of tests/golden (216 words:
               the only vocabulary file this repository carries; the key frames then hold at most 216 words each, the count is the same)
+--scoring: the scoring object of the `query` measurement (orbhip_kfdb_set_scoring: 0 L1, 1 L2, 2 chi-square, 4 Bhattacharyya, 5 dot product), with BowVectors
+normalised as that scoring's transform leaves them; the `reloc` sequence runs under the vocabulary file's own scoring.
+Every timed call is synchronous: it returns behind a synchronise of its stream, after the device has delivered the hits.
 Scanned bytes = the word ids of every live key frame (4 B each) + the slot records: what k_kfdb_scan must read; weights are read for shared words only."""
 import argparse
 import json
@@ -30,6 +33,11 @@ def bow(rng, nwords, n):
     return ids, v / v.sum()
 
 
+def normalise(scoring, v):
+    """ScoringObject.h:73-90: L2 for L2_NORM, none for DOT_PRODUCT, L1 otherwise"""
+    return v / np.sqrt(np.sum(v * v)) if scoring == 1 else v if scoring == 5 else v / v.sum()
+
+
 def timed(fn, reps):
     fn()
     t = []
@@ -43,23 +51,25 @@ def main():
     ap.add_argument("--kfs", type=int, default=10000)
     ap.add_argument("--words", type=int, default=1500)
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--scoring", type=int, default=0, choices=[0, 1, 2, 4, 5])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     rng = np.random.default_rng(1)
-    res = {"kfs": a.kfs, "words": a.words}
+    res = {"kfs": a.kfs, "words": a.words, "scoring": a.scoring}
     # ---- query
     nwords = 10**6
     pool = rng.choice(nwords, 20 * a.words, replace=False)                  # the key frames and the query draw from one pool: they share words
     db = orb_slam2_amd.KeyFrameDatabase(nwords)
+    db.set_scoring(a.scoring)
     total = 0
     t0 = time.perf_counter()
     for k in range(a.kfs):
         ids = np.unique(rng.choice(pool, int(a.words * rng.uniform(0.8, 1.2)), replace=False)).astype(np.uint32)
         v = rng.random(len(ids)) + 1e-3
-        db.add(ids, v / v.sum()); total += len(ids)
+        db.add(ids, normalise(a.scoring, v)); total += len(ids)
     res["add_ms_per_key_frame"] = (time.perf_counter() - t0) * 1e3 / a.kfs
     q = np.unique(rng.choice(pool, a.words, replace=False)).astype(np.uint32)
-    qv = rng.random(len(q)) + 1e-3; qv /= qv.sum()
+    qv = normalise(a.scoring, rng.random(len(q)) + 1e-3)
     qid = [1]
 
     def one():
@@ -91,6 +101,7 @@ def main():
     cand, nh = seq()
     med, best = timed(seq, a.reps)
     res["reloc_sequence"] = {"ms_median": med, "ms_min": best, "key_frame_words": total, "nhits": int(nh), "ncandidates": int(len(cand)), "vocabulary_words": voc.size()}
+    orb_slam2_amd.orbhip.device_synchronize(0)
     line = json.dumps(res)
     print(line)
     if a.out:
