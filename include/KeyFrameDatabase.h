@@ -44,6 +44,10 @@ public:
     // Relocalization
     std::vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F);
 
+    // Relocalization of a batch of frames: ONE device call for the queries (orbhip_kfdb_query_batch), the hits' best covisibles, ONE for the
+    // selections.  Result [i] is what DetectRelocalizationCandidates(vpF[i]) returns when the frames are asked one after another in this order.
+    std::vector<std::vector<KeyFrame*> > DetectRelocalizationCandidates(const std::vector<Frame*> &vpF);
+
 protected:
 
     // one device query (kind: ORBHIP_KFDB_RELOC / ORBHIP_KFDB_LOOP), the hits' best covisibles, the covisibility selection
@@ -63,6 +67,9 @@ protected:
 
     // Mutex (the slot mapping; the device database has its own lock)
     std::mutex mMutex;
+
+    // Held over a device query; the batched form holds it until its selections are done, since any later query supersedes a batch's snapshot
+    std::mutex mMutexQuery;
 
 private:
     KeyFrameDatabase(const KeyFrameDatabase&);

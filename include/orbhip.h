@@ -492,6 +492,36 @@ orbhip_status orbhip_kfdb_scores(orbhip_kfdb* db, const uint32_t* bow_id, const 
    out_slots = vpLoopCandidates / vpRelocCandidates. */
 orbhip_status orbhip_kfdb_select(orbhip_kfdb* db, int kind, uint64_t qid, int min_common, float min_score, const orbhip_kfdb_hit* hits, int nhits,
                                  const int32_t* neigh_off, const int32_t* neigh_slot, int32_t* out_slots, int cap, int* nout);
+/* BATCHED queries: nq queries of one kind answered IN ORDER under one hold of the database's lock, with a fixed number of launches and
+   synchronisations; every answer and the key frames' state are exactly those of nq orbhip_kfdb_query calls issued one after another (repeated qids, a
+   qid that an earlier call left in the state and, for LOOP, excluded lists that differ from query to query included).  Query i is the CSR range
+   [bow_off[i], bow_off[i+1]) of (bow_id, bow_val); its excluded slots (LOOP only; excl_off / excl_slot may be NULL for RELOC) the range
+   [excl_off[i], excl_off[i+1]) of excl_slot, its minScore min_score[i] (LOOP only).  hit_off[0 .. nq] always receives the true offsets of the
+   queries' hit lists, nsharing[i] / min_common[i] (each may be NULL) what orbhip_kfdb_query returns.  With hits != NULL and cap >= hit_off[nq] the
+   hit lists arrive in the same call; with hits == NULL the call returns ORBHIP_OK, with too small a cap ORBHIP_ERR_CAPACITY, and in both cases the
+   hits stay on the device for orbhip_kfdb_batch_hits and the key frames' state is that of the completed batch.  nq == 0 does nothing.
+   A bad argument or a bad BowVector in any query fails the whole batch before anything on the device changes.
+   Workspace: 25 bytes per cell of nq x slot capacity (the slot capacity is the number of slots ever in use at once, rounded up to a power of two,
+   at least 64): per (query, slot) the shared-word count, the first shared word, the score and the SNAPSHOT - the slot's state right after that
+   query.  More than 2^27 cells return ORBHIP_ERR_UNSUPPORTED with nothing changed: split the batch.
+   *batch_token names the snapshot for orbhip_kfdb_batch_hits and orbhip_kfdb_select_batch; the next query of any form or orbhip_kfdb_clear on the
+   database supersedes it (ORBHIP_ERR_INVALID from then on).  orbhip_kfdb_add / _erase in between are allowed. */
+orbhip_status orbhip_kfdb_query_batch(orbhip_kfdb* db, int kind, int nq, const uint64_t* qids, const int32_t* bow_off, const uint32_t* bow_id, const double* bow_val,
+                                      const int32_t* excl_off, const int32_t* excl_slot, const float* min_score,
+                                      int32_t* hit_off, int32_t* nsharing, int32_t* min_common, orbhip_kfdb_hit* hits, int cap, uint64_t* batch_token);
+/* ... with query i read where orbhip_compute_bow(ctx, voc, ...) left frame first_frame + i, on the extractor's stream: only the nq lengths are downloaded
+   (the host plans the scan's tiles from them), no BowVector travels */
+orbhip_status orbhip_kfdb_query_frames(orbhip_kfdb* db, int kind, const uint64_t* qids, orbhip_ctx* ctx, orbhip_voc* voc, int first_frame, int nq,
+                                       const int32_t* excl_off, const int32_t* excl_slot, const float* min_score,
+                                       int32_t* hit_off, int32_t* nsharing, int32_t* min_common, orbhip_kfdb_hit* hits, int cap, uint64_t* batch_token);
+/* the hit lists of the queries [first_query, first_query + nqueries) of the batch, as they lie between its hit_off entries */
+orbhip_status orbhip_kfdb_batch_hits(orbhip_kfdb* db, uint64_t batch_token, int first_query, int nqueries, orbhip_kfdb_hit* hits, int cap);
+/* orbhip_kfdb_select for every query of the batch: hits / hit_off as the query returned them, the neighbours of hit h (counted through the whole
+   batch) neigh_slot[neigh_off[h] .. neigh_off[h+1]); query i's candidates are out_slots[out_off[i] .. out_off[i+1]).  Query i reads its neighbours'
+   state as it stood right after query i (the snapshot), not after the batch; liveness is read at the time of this call, and a key frame added since
+   the batch has a new key frame's state.  With more than `cap` candidates out_off is still complete and the call returns ORBHIP_ERR_CAPACITY. */
+orbhip_status orbhip_kfdb_select_batch(orbhip_kfdb* db, uint64_t batch_token, int kind, const orbhip_kfdb_hit* hits, const int32_t* hit_off,
+                                       const int32_t* neigh_off, const int32_t* neigh_slot, int32_t* out_slots, int32_t* out_off, int cap);
 
 /* -------- distorted cameras and rectification -------------------------------------------
    Monocular / RGB-D cameras with lens distortion (TUM1-3.yaml): Frame's constructors call UndistortKeyPoints (Frame.cc:404-434)

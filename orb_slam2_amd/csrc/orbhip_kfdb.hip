@@ -13,6 +13,7 @@
 //                  above it, their order (first shared word << 32 | add sequence) and the hit list (lScoreAndMatch)
 // The covisibility accumulation (:144-196, :258-308) needs the caller's neighbour lists and is host arithmetic (orbhip_kfdb_select).
 // One lock per database, held for a whole entry: the reference's mMutex (add from LocalMapping, the queries from LoopClosing and Tracking).
+// Batches of queries (orbhip_kfdb_query_batch and its companions) have kernels of their own in the second half of this file.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
@@ -223,6 +224,10 @@ __global__ __launch_bounds__(256) void k_kfdb_gather(const KfState* state, const
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+struct KfBatch;
+static void kf_batch_free(KfBatch* b);
+static void kf_batch_supersede(KfBatch* b);
+
 struct orbhip_kfdb {
     int device = 0, nwords = 0, scoring = 0;                 // scoring: DBoW2's ScoringType of the next query (orbhip_kfdb_set_scoring)
     std::mutex m;
@@ -235,6 +240,7 @@ struct orbhip_kfdb {
     int* d_cnt = nullptr; uint32_t* d_first = nullptr; double* d_score = nullptr; int* d_flag = nullptr; unsigned long long* d_keys = nullptr; int* d_pay = nullptr;
     orbhip_kfdb_hit* d_hits = nullptr; int* d_meta = nullptr; uint32_t* d_qid = nullptr; double* d_qval = nullptr;
     int* d_list = nullptr; size_t list_cap = 0; KfState* d_gather = nullptr; size_t gather_cap = 0;
+    uint64_t batch_tokens = 0; KfBatch* batch = nullptr;                           // the batched queries' workspace and snapshot (below), made by the first orbhip_kfdb_query_batch
 };
 
 static void kf_free(void* p) { if (p) (void)hipFree(p); }
@@ -297,6 +303,7 @@ extern "C" void orbhip_kfdb_destroy(orbhip_kfdb* db)
     void* ptrs[] = {db->d_ids, db->d_vals, db->d_slots, db->d_state[0], db->d_state[1], db->d_cnt, db->d_first, db->d_score, db->d_flag, db->d_keys, db->d_pay, db->d_hits,
                     db->d_meta, db->d_qid, db->d_qval, db->d_list, db->d_gather};
     for (void* p : ptrs) kf_free(p);
+    kf_batch_free(db->batch);
     delete db;
 }
 
@@ -305,6 +312,7 @@ extern "C" orbhip_status orbhip_kfdb_clear(orbhip_kfdb* db)
     if (!db) return orbhip_set_error(ORBHIP_ERR_INVALID, "null database");
     std::lock_guard<std::mutex> lock(db->m);
     db->nslots = 0; db->nlive = 0; db->arena_end = 0; db->holes.clear(); db->h_slots.clear(); db->free_slots.clear();
+    kf_batch_supersede(db->batch);
     return ORBHIP_OK;
 }
 
@@ -415,6 +423,7 @@ static orbhip_status kf_query_core(orbhip_kfdb* db, int kind, unsigned long long
                                    const int* excl, int nexcl, float min_score, orbhip_kfdb_hit* hits, int cap, int* nhits, int* nsharing, int* min_common, hipStream_t s)
 {
     *nhits = 0; if (nsharing) *nsharing = 0; if (min_common) *min_common = 0;
+    kf_batch_supersede(db->batch);                                            // a batch's snapshot describes the state its own queries left
     if (db->nslots == 0) return ORBHIP_OK;
     int ne = 0;
     if (kind == ORBHIP_KFDB_LOOP && nexcl > 0) {
@@ -521,6 +530,31 @@ extern "C" orbhip_status orbhip_kfdb_scores(orbhip_kfdb* db, const uint32_t* bow
     return ORBHIP_OK;
 }
 
+// The covisibility accumulation over gathered neighbour states: list[j] the neighbour's slot (< 0: not in the database), ns[j] its state, j as neigh_off counts
+static void kf_select_host(int kind, unsigned long long qid, int min_common, float min_score, const orbhip_kfdb_hit* hits, int nhits,
+                           const int32_t* neigh_off, const int* list, const KfState* ns, int nslots, std::vector<int>& picked)
+{
+    std::vector<float> acc((size_t)nhits); std::vector<int> best((size_t)nhits);
+    float best_acc = kind == ORBHIP_KFDB_LOOP ? min_score : 0.0f;
+    for (int i = 0; i < nhits; i++) {
+        float best_score = hits[i].score, a = hits[i].score; int best_slot = hits[i].slot;
+        for (int j = neigh_off[i]; j < neigh_off[i + 1]; j++) {
+            if (list[j] < 0) continue;
+            const KfState& st = ns[j];
+            if (st.query != qid) continue;
+            if (kind == ORBHIP_KFDB_LOOP && !(st.words > min_common)) continue;
+            a += st.score;
+            if (st.score > best_score) { best_slot = list[j]; best_score = st.score; }
+        }
+        acc[i] = a; best[i] = best_slot;
+        if (a > best_acc) best_acc = a;
+    }
+    const float retain = 0.75f * best_acc;
+    picked.clear(); std::vector<char> seen((size_t)nslots, 0);                             // first occurrence wins (spAlreadyAddedKF)
+    for (int i = 0; i < nhits; i++)
+        if (acc[i] > retain && !seen[best[i]]) { seen[best[i]] = 1; picked.push_back(best[i]); }
+}
+
 // The covisibility accumulation (KeyFrameDatabase.cc:144-196 LOOP, :258-308 RELOC): f32 sums in neighbour order over the state the query left.
 extern "C" orbhip_status orbhip_kfdb_select(orbhip_kfdb* db, int kind, uint64_t qid, int min_common, float min_score, const orbhip_kfdb_hit* hits, int nhits,
                                             const int32_t* neigh_off, const int32_t* neigh_slot, int32_t* out_slots, int cap, int* nout)
@@ -552,27 +586,548 @@ extern "C" orbhip_status orbhip_kfdb_select(orbhip_kfdb* db, int kind, uint64_t 
             KFCHK(hipStreamSynchronize(s));
         }
     }
-    std::vector<float> acc((size_t)nhits); std::vector<int> best((size_t)nhits);
-    float best_acc = kind == ORBHIP_KFDB_LOOP ? min_score : 0.0f;
-    for (int i = 0; i < nhits; i++) {
-        float best_score = hits[i].score, a = hits[i].score; int best_slot = hits[i].slot;
-        for (int j = neigh_off[i]; j < neigh_off[i + 1]; j++) {
-            if (list[j] < 0) continue;
-            const KfState& st = ns[j];
-            if (st.query != qid) continue;
-            if (kind == ORBHIP_KFDB_LOOP && !(st.words > min_common)) continue;
-            a += st.score;
-            if (st.score > best_score) { best_slot = list[j]; best_score = st.score; }
-        }
-        acc[i] = a; best[i] = best_slot;
-        if (a > best_acc) best_acc = a;
-    }
-    const float retain = 0.75f * best_acc;
-    std::vector<int> picked; std::vector<char> seen((size_t)nslots, 0);                             // first occurrence wins (spAlreadyAddedKF)
-    for (int i = 0; i < nhits; i++)
-        if (acc[i] > retain && !seen[best[i]]) { seen[best[i]] = 1; picked.push_back(best[i]); }
+    std::vector<int> picked;
+    kf_select_host(kind, qid, min_common, min_score, hits, nhits, neigh_off, list.data(), ns.data(), nslots, picked);
     *nout = (int)picked.size();
     if (*nout > cap) return orbhip_set_error(ORBHIP_ERR_CAPACITY, "key-frame database: %d candidates, room for %d", *nout, cap);
     for (size_t i = 0; i < picked.size(); i++) out_slots[i] = picked[i];
+    return ORBHIP_OK;
+}
+
+// ================================================================================================ batched queries
+// orbhip_kfdb_query_batch / _query_frames answer nq queries in order under one hold of the lock with a fixed number of launches:
+//   k_kfdb_scan_batch   a workgroup stages a TILE of queries' id lists in LDS (the host plans the tiles: at most KB_TQ queries and KB_IDS ids) and its four waves
+//                       own a key frame each, several in turn; per (query, key frame) the count, the first shared word and the score of k_kfdb_scan, into
+//                       [query][slot] matrices.  Tiles are the fast grid index, so the workgroups that read one key frame run together and its words come from HBM once.
+//   k_kfdb_walk_words   one thread per slot steps through the queries in order with {query, words} in registers: k_kfdb_select's rule; the listed words
+//                       replace the counts, the per-query maximum and listed count are reduced, and the snapshot's {query == qid, words} are written
+//   k_kfdb_walk_score   the same walk for the score once every query's minCommonWords is known; snapshot's score, per-query hit counts
+//   k_kfdb_sort_batch   one workgroup per query: compaction of its hits, their order, the hit list at its CSR offset
+// The SNAPSHOT is, per (query, slot), the slot's state right after that query; orbhip_kfdb_select_batch gathers the neighbours' states from it.
+#define KB_TQ 16                       // queries a tile holds at most
+#define KB_IDS 8192                    // ids a tile holds at most (32 KiB of LDS: one query of KFDB_MAX_WORDS always fits)
+#define KB_MAX_CELLS (1ll << 27)       // nq x slot capacity; 25 bytes of workspace per cell
+#define KB_U 8                         // queries a walk loads ahead of its dependent chain
+
+struct KfBq { long long id_off, val_off; int n, pad; };      // a query: byte offsets of its ids and weights from the batch's two base pointers, its length
+
+struct KfBscanParams {
+    const uint32_t* ids; const double* vals; const KfSlot* slots; int nslots;
+    const uint32_t* q_id; const double* q_val; const KfBq* q;          // base pointers and the queries
+    const int* tile_q0; int ntiles;                                     // tile t holds the queries [tile_q0[t], tile_q0[t + 1])
+    int groups, gpb;                                                    // groups of four slots in all, groups per workgroup
+    size_t stride;                                                      // row length of the matrices
+    int* cnt; uint32_t* first; double* score;
+};
+
+template <int SC> __global__ __launch_bounds__(KS_T) void k_kfdb_scan_batch(KfBscanParams P)
+{
+    HIP_DYNAMIC_SHARED(uint32_t, q)
+    __shared__ int s_off[KB_TQ + 1];
+    __shared__ long long s_val[KB_TQ];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int tile = blockIdx.x % P.ntiles, gb = blockIdx.x / P.ntiles;
+    const int q0 = P.tile_q0[tile], T = P.tile_q0[tile + 1] - q0;
+    if (tid == 0) {
+        int o = 0;
+        for (int t = 0; t < T; t++) { s_off[t] = o; o += P.q[q0 + t].n; s_val[t] = P.q[q0 + t].val_off; }
+        s_off[T] = o;
+    }
+    __syncthreads();
+    for (int t = 0; t < T; t++) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(P.q_id) + P.q[q0 + t].id_off);
+        const int o = s_off[t], n = s_off[t + 1] - o;
+        for (int i = tid; i < n; i += KS_T) q[o + i] = src[i];
+    }
+    __syncthreads();
+    for (int g = gb * P.gpb; g < (gb + 1) * P.gpb && g < P.groups; g++) {     // (whole waves, no barrier below)
+        const int w = g * (KS_T / 64) + (tid >> 6);
+        if (w >= P.nslots) break;
+        const KfSlot S = P.slots[w];
+        const uint32_t* kid = P.ids + S.off; const double* kval = P.vals + S.off;
+        const bool any = S.live && S.n > 0;
+        const uint32_t id0 = any && (unsigned)lane < S.n ? kid[lane] : 0xffffffffu;     // the first chunk's ids stay in a register for every query of the tile
+        for (int t = 0; t < T; t++) {
+            const uint32_t* ql = q + s_off[t]; const int nq = s_off[t + 1] - s_off[t];
+            const double* qval = reinterpret_cast<const double*>(reinterpret_cast<const char*>(P.q_val) + s_val[t]);
+            int top = 0;
+            if (nq > 0) top = 1 << (31 - __clz(nq));
+            int cnt = 0; uint32_t first = 0xffffffffu; double s = 0.0;
+            if (any && nq > 0) {
+                uint32_t id_next = id0;
+                for (unsigned base = 0; base < S.n; base += 64) {
+                    const unsigned i = base + lane; const bool in = i < S.n;
+                    const uint32_t id = id_next;
+                    id_next = i + 64 < S.n ? kid[i + 64] : 0xffffffffu;       // (after the tile's first query these come from the cache)
+                    int pos = 0;
+                    for (int st = top; st; st >>= 1) { const int p = pos + st; if (p <= nq && ql[p - 1] < id) pos = p; }
+                    const bool hit = in && pos < nq && ql[pos] == id;
+                    double term = 0.0;
+                    if (hit) { const double wi = kval[i], vi = qval[pos]; term = kf_term<SC>(vi, wi); }
+                    unsigned long long m = __ballot(hit);
+                    if (m) {
+                        if (cnt == 0) first = (uint32_t)__builtin_amdgcn_readlane((int)id, __ffsll((long long)m) - 1);
+                        cnt += __popcll(m);
+                        while (m) { const int l = __ffsll((long long)m) - 1; m &= m - 1; s = __dadd_rn(s, kf_readlane(term, l)); }      // ONE chain, ascending words
+                    }
+                }
+            }
+            if (lane == 0) { const size_t c = (size_t)(q0 + t) * P.stride + (size_t)w; P.cnt[c] = cnt; P.first[c] = first; P.score[c] = kf_result<SC>(s); }
+        }
+    }
+}
+
+struct KfBwalkParams {
+    const KfSlot* slots; KfState* state; int nslots, nq, kind; size_t stride;
+    const unsigned long long* qid; const float* min_score;
+    const int* excl_off; const int* excl;                    // LOOP: per query the excluded slots, ascending
+    int* cnt;                                                // in: shared words; out: words of a listed key frame, 0 otherwise
+    const double* score;
+    int* qmax; int* qnlist; int* qnhit;                      // per query
+    int* s_words; float* s_score; unsigned char* s_match;    // the snapshot
+};
+
+__global__ __launch_bounds__(256) void k_kfdb_walk_words(KfBwalkParams P)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool in = i < P.nslots;
+    const size_t col = in ? (size_t)i : 0;
+    const bool live = in && P.slots[col].live;
+    unsigned long long query = P.state[col].query; int words = P.state[col].words;
+    for (int qb = 0; qb < P.nq; qb += KB_U) {
+        int c[KB_U];
+#pragma unroll
+        for (int u = 0; u < KB_U; u++) c[u] = (live && qb + u < P.nq) ? P.cnt[(size_t)(qb + u) * P.stride + col] : 0;
+#pragma unroll
+        for (int u = 0; u < KB_U; u++) {
+            const int qi = qb + u;
+            if (qi >= P.nq) break;                                                                // (uniform)
+            const unsigned long long qid = P.qid[qi];
+            int listed = 0;
+            if (c[u] >= 1) {
+                if (query == qid) words += c[u];
+                else {
+                    bool excluded = false;
+                    if (P.kind == ORBHIP_KFDB_LOOP) {
+                        int lo = P.excl_off[qi]; const int end = P.excl_off[qi + 1]; int hi = end;
+                        while (lo < hi) { const int mid = (lo + hi) >> 1; if (P.excl[mid] < i) lo = mid + 1; else hi = mid; }
+                        excluded = lo < end && P.excl[lo] == i;
+                    }
+                    if (excluded) words = 1;
+                    else { query = qid; words = c[u]; listed = c[u]; }
+                }
+            }
+            if (in) {
+                const size_t cell = (size_t)qi * P.stride + col;
+                P.cnt[cell] = listed; P.s_words[cell] = words; P.s_match[cell] = query == qid;
+            }
+            int lmax = listed, nl = listed != 0;
+            for (int o = 32; o; o >>= 1) { lmax = max(lmax, __shfl_xor(lmax, o)); nl += __shfl_xor(nl, o); }
+            if (lane == 0 && nl) { atomicMax(&P.qmax[qi], lmax); atomicAdd(&P.qnlist[qi], nl); }
+        }
+    }
+    if (in) { P.state[col].query = query; P.state[col].words = words; }
+}
+
+__global__ __launch_bounds__(256) void k_kfdb_walk_score(KfBwalkParams P)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool in = i < P.nslots;
+    const size_t col = in ? (size_t)i : 0;
+    float score = P.state[col].score;
+    for (int qb = 0; qb < P.nq; qb += KB_U) {
+        int l[KB_U];
+#pragma unroll
+        for (int u = 0; u < KB_U; u++) l[u] = (in && qb + u < P.nq) ? P.cnt[(size_t)(qb + u) * P.stride + col] : 0;
+#pragma unroll
+        for (int u = 0; u < KB_U; u++) {
+            const int qi = qb + u;
+            if (qi >= P.nq) break;
+            const int minc = (int)__fmul_rn((float)P.qmax[qi], 0.8f);
+            const size_t cell = (size_t)qi * P.stride + col;
+            bool hit = false;
+            if (l[u] > minc) { score = (float)P.score[cell]; hit = P.kind == ORBHIP_KFDB_RELOC || score >= P.min_score[qi]; }
+            if (in) P.s_score[cell] = score;
+            const unsigned long long m = __ballot(hit);
+            if (lane == 0 && m) atomicAdd(&P.qnhit[qi], (int)__popcll(m));
+        }
+    }
+    if (in) P.state[col].score = score;
+}
+
+struct KfBsortParams {
+    const KfSlot* slots; int nslots, kind; size_t stride;
+    const int* cnt; const uint32_t* first; const double* score;      // cnt: the listed words
+    const float* min_score; const int* qmax; const int* qnhit;
+    const int* hit_off; const long long* key_off;            // per query: where its hits go; where its sort workspace lies (< 0: the LDS)
+    unsigned long long* keys; int* pay; orbhip_kfdb_hit* hits;
+};
+
+__global__ __launch_bounds__(KSEL_T) void k_kfdb_sort_batch(KfBsortParams P)
+{
+    __shared__ int s_nhit;
+    __shared__ unsigned long long s_key[KSEL_LDS];
+    __shared__ int s_pay[KSEL_LDS];
+    const int tid = threadIdx.x, lane = tid & 63, qi = blockIdx.x;
+    const int n = P.qnhit[qi];
+    if (n == 0) return;                                                                           // (the whole workgroup)
+    if (tid == 0) s_nhit = 0;
+    __syncthreads();
+    const int minc = (int)__fmul_rn((float)P.qmax[qi], 0.8f);
+    const float min_score = P.min_score[qi];
+    const long long ko = P.key_off[qi];
+    const bool in_lds = ko < 0;
+    unsigned long long* gkey = P.keys + (in_lds ? 0 : ko); int* gpay = P.pay + (in_lds ? 0 : ko);
+    const int* cnt = P.cnt + (size_t)qi * P.stride; const uint32_t* first = P.first + (size_t)qi * P.stride; const double* score = P.score + (size_t)qi * P.stride;
+    for (int b = 0; b < P.nslots; b += KSEL_T) {
+        const int i = b + tid;
+        bool hit = false; unsigned long long key = 0;
+        if (i < P.nslots && cnt[i] > minc) {
+            hit = P.kind == ORBHIP_KFDB_RELOC || (float)score[i] >= min_score;
+            key = ((unsigned long long)first[i] << 32) | P.slots[i].seq;
+        }
+        const unsigned long long m = __ballot(hit);
+        if (m) {
+            const int leader = __ffsll((long long)m) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&s_nhit, (int)__popcll(m));
+            base = __builtin_amdgcn_readlane(base, leader);
+            const int pos = base + (int)__popcll(m & ((1ull << lane) - 1ull));
+            if (hit && pos < n) { if (in_lds) { s_key[pos] = key; s_pay[pos] = i; } else { gkey[pos] = key; gpay[pos] = i; } }
+        }
+    }
+    __syncthreads();
+    int n2 = 1; while (n2 < n) n2 <<= 1;
+    orbhip_kfdb_hit* out = P.hits + P.hit_off[qi];
+    if (in_lds) {
+        for (int t = n + tid; t < n2; t += KSEL_T) { s_key[t] = ~0ull; s_pay[t] = 0; }
+        __syncthreads();
+        kf_bitonic(s_key, s_pay, n2, tid);
+        for (int t = tid; t < n; t += KSEL_T) { const int slot = s_pay[t]; orbhip_kfdb_hit h; h.slot = slot; h.words = cnt[slot]; h.score = (float)score[slot]; out[t] = h; }
+    } else {
+        for (int t = n + tid; t < n2; t += KSEL_T) { gkey[t] = ~0ull; gpay[t] = 0; }
+        __syncthreads();
+        kf_bitonic(gkey, gpay, n2, tid);
+        for (int t = tid; t < n; t += KSEL_T) { const int slot = gpay[t]; orbhip_kfdb_hit h; h.slot = slot; h.words = cnt[slot]; h.score = (float)score[slot]; out[t] = h; }
+    }
+}
+
+// the snapshot's cells named by list (cell index, < 0: zeros) as KfState: query = 1 where the slot's query was the cell's query id
+__global__ __launch_bounds__(256) void k_kfdb_gather_batch(const int* s_words, const float* s_score, const unsigned char* s_match, const long long* list, int n, KfState* out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long cell = list[i];
+    unsigned long long query = 0; int words = 0; float score = 0.0f;
+    if (cell >= 0) { query = s_match[cell]; words = s_words[cell]; score = s_score[cell]; }
+    out[i].query = query; out[i].words = words; out[i].score = score;
+}
+
+struct KfBatch {
+    // workspace: the matrices, the per-query arrays, the uploaded batch
+    int* d_cnt = nullptr; uint32_t* d_first = nullptr; double* d_score = nullptr; int* d_swords = nullptr; float* d_sscore = nullptr; unsigned char* d_smatch = nullptr; size_t cells = 0;
+    int* d_meta = nullptr; size_t meta_cap = 0;                                                  // qmax, qnlist, qnhit: nq each
+    uint32_t* d_qid = nullptr; size_t qid_cap = 0; double* d_qval = nullptr; size_t qval_cap = 0;
+    KfBq* d_q = nullptr; size_t q_cap = 0; int* d_tile = nullptr; size_t tile_cap = 0; unsigned long long* d_qids = nullptr; size_t qids_cap = 0; float* d_minscore = nullptr; size_t minscore_cap = 0;
+    int* d_excl_off = nullptr; size_t excl_off_cap = 0; int* d_excl = nullptr; size_t excl_cap = 0; int* d_lens = nullptr; size_t lens_cap = 0;
+    int* d_hit_off = nullptr; size_t hit_off_cap = 0; long long* d_key_off = nullptr; size_t key_off_cap = 0;
+    unsigned long long* d_keys = nullptr; size_t keys_cap = 0; int* d_pay = nullptr; size_t pay_cap = 0; orbhip_kfdb_hit* d_hits = nullptr; size_t hits_cap = 0;
+    long long* d_cells = nullptr; size_t cells_cap = 0; KfState* d_gather = nullptr; size_t gather_cap = 0;
+    // the snapshot's books
+    bool valid = false; uint64_t token = 0; int kind = 0, nq = 0, nslots = 0; size_t stride = 0; unsigned next_seq = 0;
+    std::vector<unsigned long long> qid; std::vector<float> min_score; std::vector<int> min_common, hit_off;
+};
+
+static void kf_batch_free(KfBatch* b)
+{
+    if (!b) return;
+    void* ptrs[] = {b->d_cnt, b->d_first, b->d_score, b->d_swords, b->d_sscore, b->d_smatch, b->d_meta, b->d_qid, b->d_qval, b->d_q, b->d_tile, b->d_qids, b->d_minscore, b->d_excl_off, b->d_excl,
+                    b->d_lens, b->d_hit_off, b->d_key_off, b->d_keys, b->d_pay, b->d_hits, b->d_cells, b->d_gather};
+    for (void* p : ptrs) kf_free(p);
+    delete b;
+}
+static void kf_batch_supersede(KfBatch* b) { if (b) b->valid = false; }
+
+template <typename T> static hipError_t kf_fit(T** p, size_t* cap, size_t need)                  // exactly `need` elements when the array is too small (the matrices are large)
+{
+    if (need <= *cap) return hipSuccess;
+    kf_free(*p); *p = nullptr; *cap = 0;
+    const hipError_t e = orbhip_dmalloc((void**)p, need * sizeof(T));
+    if (e == hipSuccess) *cap = need;
+    return e;
+}
+template <typename T> static hipError_t kf_put(T** p, size_t* cap, const std::vector<T>& v, hipStream_t s)      // v stays until the stream is drained
+{
+    hipError_t e = kf_grow(p, cap, std::max<size_t>(v.size(), 1)); if (e != hipSuccess) return e;
+    if (!v.empty()) e = hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
+    return e;
+}
+
+// The batch on stream s, the database's lock held: the queries' BowVectors are on the device (ids at q_id + bq[i].id_off, weights at q_val + bq[i].val_off).
+static orbhip_status kf_batch_core(orbhip_kfdb* db, int kind, int nq, const uint64_t* qids, const uint32_t* d_qid, const double* d_qval, const std::vector<KfBq>& bq,
+                                   const int32_t* excl_off, const int32_t* excl_slot, const float* min_score,
+                                   int32_t* hit_off, int32_t* nsharing, int32_t* min_common, orbhip_kfdb_hit* hits, int cap, uint64_t* token, hipStream_t s)
+{
+    KfBatch* B = db->batch;
+    B->valid = false;
+    const int nslots = db->nslots; const size_t stride = ((size_t)nslots + 63) & ~(size_t)63, cells = (size_t)nq * stride;
+    B->qid.assign(qids, qids + nq);
+    B->min_score.assign((size_t)nq, 0.0f); if (kind == ORBHIP_KFDB_LOOP) B->min_score.assign(min_score, min_score + nq);
+    B->min_common.assign((size_t)nq, 0); B->hit_off.assign((size_t)nq + 1, 0);
+    std::vector<int> meta((size_t)3 * nq, 0);
+    if (nslots > 0) {
+        // the tiles: consecutive queries while their ids fit
+        std::vector<int> tile(1, 0); int ids = 0, maxids = 1;
+        for (int i = 0; i < nq; i++) {
+            if (i > tile.back() && (i - tile.back() == KB_TQ || ids + bq[i].n > KB_IDS)) { tile.push_back(i); ids = 0; }
+            ids += bq[i].n; maxids = std::max(maxids, ids);
+        }
+        tile.push_back(nq);
+        const int ntiles = (int)tile.size() - 1;
+        std::vector<int> eoff((size_t)nq + 1, 0), excl;
+        if (kind == ORBHIP_KFDB_LOOP)
+            for (int i = 0; i < nq; i++) {
+                const size_t b = excl.size();
+                for (int j = excl_off[i]; j < excl_off[i + 1]; j++) if (excl_slot[j] >= 0 && excl_slot[j] < nslots) excl.push_back(excl_slot[j]);
+                std::sort(excl.begin() + b, excl.end()); excl.erase(std::unique(excl.begin() + b, excl.end()), excl.end());
+                eoff[i + 1] = (int)excl.size();
+            }
+        if (cells > B->cells) {                                           // the six matrices grow together
+            size_t c[6] = {0, 0, 0, 0, 0, 0}; B->cells = 0;
+            KFCHK(kf_fit(&B->d_cnt, &c[0], cells)); KFCHK(kf_fit(&B->d_first, &c[1], cells)); KFCHK(kf_fit(&B->d_score, &c[2], cells));
+            KFCHK(kf_fit(&B->d_swords, &c[3], cells)); KFCHK(kf_fit(&B->d_sscore, &c[4], cells)); KFCHK(kf_fit(&B->d_smatch, &c[5], cells));
+            B->cells = cells;
+        }
+        std::vector<unsigned long long> q64(qids, qids + nq);
+        KFCHK(kf_put(&B->d_q, &B->q_cap, bq, s)); KFCHK(kf_put(&B->d_tile, &B->tile_cap, tile, s)); KFCHK(kf_put(&B->d_qids, &B->qids_cap, q64, s));
+        KFCHK(kf_put(&B->d_minscore, &B->minscore_cap, B->min_score, s)); KFCHK(kf_put(&B->d_excl_off, &B->excl_off_cap, eoff, s)); KFCHK(kf_put(&B->d_excl, &B->excl_cap, excl, s));
+        KFCHK(kf_grow(&B->d_meta, &B->meta_cap, meta.size()));
+        KFCHK(hipMemsetAsync(B->d_meta, 0, meta.size() * sizeof(int), s));
+        KfBscanParams P; memset(&P, 0, sizeof P);
+        P.ids = db->d_ids; P.vals = db->d_vals; P.slots = db->d_slots; P.nslots = nslots; P.q_id = d_qid; P.q_val = d_qval; P.q = B->d_q; P.tile_q0 = B->d_tile; P.ntiles = ntiles;
+        P.groups = (nslots + KS_T / 64 - 1) / (KS_T / 64);
+        P.gpb = (int)std::min<long long>(16, std::max<long long>(1, (long long)P.groups * ntiles / 8192));      // enough workgroups to fill the device, then fewer stagings of the tile
+        P.stride = stride; P.cnt = B->d_cnt; P.first = B->d_first; P.score = B->d_score;
+        const long long nblocks = (long long)((P.groups + P.gpb - 1) / P.gpb) * ntiles;
+        if (nblocks > 0x7fffffffll) return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "key-frame database: a batch of %lld workgroups", nblocks);
+        const dim3 g((unsigned)nblocks, 1, 1), b(KS_T, 1, 1); const size_t lds = (size_t)maxids * sizeof(uint32_t);
+        switch (db->scoring) {
+        case 1: hipLaunchKernelGGL(k_kfdb_scan_batch<1>, g, b, lds, s, P); break;
+        case 2: hipLaunchKernelGGL(k_kfdb_scan_batch<2>, g, b, lds, s, P); break;
+        case 4: hipLaunchKernelGGL(k_kfdb_scan_batch<4>, g, b, lds, s, P); break;
+        case 5: hipLaunchKernelGGL(k_kfdb_scan_batch<5>, g, b, lds, s, P); break;
+        default: hipLaunchKernelGGL(k_kfdb_scan_batch<0>, g, b, lds, s, P); break;
+        }
+        KFCHK(hipGetLastError());
+        KfBwalkParams W; memset(&W, 0, sizeof W);
+        W.slots = db->d_slots; W.state = db->d_state[kind]; W.nslots = nslots; W.nq = nq; W.kind = kind; W.stride = stride; W.qid = B->d_qids; W.min_score = B->d_minscore;
+        W.excl_off = B->d_excl_off; W.excl = B->d_excl; W.cnt = B->d_cnt; W.score = B->d_score; W.qmax = B->d_meta; W.qnlist = B->d_meta + nq; W.qnhit = B->d_meta + 2 * (size_t)nq;
+        W.s_words = B->d_swords; W.s_score = B->d_sscore; W.s_match = B->d_smatch;
+        const dim3 wg((unsigned)((nslots + 255) / 256), 1, 1), wb(256, 1, 1);
+        hipLaunchKernelGGL(k_kfdb_walk_words, wg, wb, 0, s, W);
+        hipLaunchKernelGGL(k_kfdb_walk_score, wg, wb, 0, s, W);
+        KFCHK(hipGetLastError());
+        KFCHK(hipMemcpyAsync(meta.data(), B->d_meta, meta.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        KFCHK(hipStreamSynchronize(s));                                   // the key frames' state is that of the completed batch from here on
+        std::vector<long long> koff((size_t)nq, -1); long long nkeys = 0;
+        for (int i = 0; i < nq; i++) {
+            const int nh = meta[2 * (size_t)nq + i];
+            if (nh < 0 || nh > nslots) return orbhip_set_error(ORBHIP_ERR_HIP, "key-frame database: %d hits among %d slots", nh, nslots);
+            B->hit_off[i + 1] = B->hit_off[i] + nh;
+            B->min_common[i] = meta[(size_t)nq + i] ? (int)((float)meta[i] * 0.8f) : 0;
+            if (nh > KSEL_LDS) { koff[i] = nkeys; long long n2 = 1; while (n2 < nh) n2 <<= 1; nkeys += n2; }
+        }
+        const int total = B->hit_off[nq];
+        if (total > 0) {
+            KFCHK(kf_put(&B->d_hit_off, &B->hit_off_cap, B->hit_off, s)); KFCHK(kf_put(&B->d_key_off, &B->key_off_cap, koff, s));
+            KFCHK(kf_grow(&B->d_keys, &B->keys_cap, (size_t)std::max<long long>(nkeys, 1))); KFCHK(kf_grow(&B->d_pay, &B->pay_cap, (size_t)std::max<long long>(nkeys, 1)));
+            KFCHK(kf_grow(&B->d_hits, &B->hits_cap, (size_t)total));
+            KfBsortParams Q; memset(&Q, 0, sizeof Q);
+            Q.slots = db->d_slots; Q.nslots = nslots; Q.kind = kind; Q.stride = stride; Q.cnt = B->d_cnt; Q.first = B->d_first; Q.score = B->d_score; Q.min_score = B->d_minscore;
+            Q.qmax = B->d_meta; Q.qnhit = B->d_meta + 2 * (size_t)nq; Q.hit_off = B->d_hit_off; Q.key_off = B->d_key_off; Q.keys = B->d_keys; Q.pay = B->d_pay; Q.hits = B->d_hits;
+            hipLaunchKernelGGL(k_kfdb_sort_batch, dim3((unsigned)nq, 1, 1), dim3(KSEL_T, 1, 1), 0, s, Q);
+            KFCHK(hipGetLastError());
+            if (hits && cap >= total) KFCHK(hipMemcpyAsync(hits, B->d_hits, (size_t)total * sizeof(orbhip_kfdb_hit), hipMemcpyDeviceToHost, s));
+            KFCHK(hipStreamSynchronize(s));
+        }
+    }
+    for (int i = 0; i <= nq; i++) hit_off[i] = B->hit_off[i];
+    for (int i = 0; i < nq; i++) { if (nsharing) nsharing[i] = meta[(size_t)nq + i]; if (min_common) min_common[i] = B->min_common[i]; }
+    B->kind = kind; B->nq = nq; B->nslots = nslots; B->stride = stride; B->next_seq = db->next_seq; B->token = ++db->batch_tokens; B->valid = true;
+    *token = B->token;
+    if (hits && cap < B->hit_off[nq])
+        return orbhip_set_error(ORBHIP_ERR_CAPACITY, "key-frame database: %d hits, room for %d (the key frames' state is that of the completed batch; orbhip_kfdb_batch_hits delivers)", B->hit_off[nq], cap);
+    return ORBHIP_OK;
+}
+
+static orbhip_status kf_batch_args(orbhip_kfdb* db, int kind, int nq, const uint64_t* qids, const int32_t* excl_off, const int32_t* excl_slot, const float* min_score,
+                                   int32_t* hit_off, int cap, uint64_t* token)
+{
+    if (!db || !token || nq < 0 || cap < 0 || (kind != ORBHIP_KFDB_RELOC && kind != ORBHIP_KFDB_LOOP) || !hit_off || (nq > 0 && !qids))
+        return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    if (kind == ORBHIP_KFDB_LOOP && nq > 0) {
+        if (!excl_off || !min_score || excl_off[0] != 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "a LOOP batch needs excluded lists and minimum scores");
+        for (int i = 0; i < nq; i++) if (excl_off[i + 1] < excl_off[i]) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad excluded lists");
+        if (excl_off[nq] > 0 && !excl_slot) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad excluded lists");
+    }
+    return ORBHIP_OK;
+}
+
+static orbhip_status kf_batch_room(orbhip_kfdb* db, int nq)       // the lock held
+{
+    if ((long long)nq * (long long)std::max(db->slot_cap, 64) > KB_MAX_CELLS)
+        return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "key-frame database: %d queries x %d slots exceed %lld cells: split the batch", nq, std::max(db->slot_cap, 64), (long long)KB_MAX_CELLS);
+    if (!db->batch) db->batch = new KfBatch();
+    return ORBHIP_OK;
+}
+
+extern "C" orbhip_status orbhip_kfdb_query_batch(orbhip_kfdb* db, int kind, int nq, const uint64_t* qids, const int32_t* bow_off, const uint32_t* bow_id, const double* bow_val,
+                                                 const int32_t* excl_off, const int32_t* excl_slot, const float* min_score,
+                                                 int32_t* hit_off, int32_t* nsharing, int32_t* min_common, orbhip_kfdb_hit* hits, int cap, uint64_t* batch_token)
+{
+    OrbApiTimer api_timer;
+    orbhip_status st = kf_batch_args(db, kind, nq, qids, excl_off, excl_slot, min_score, hit_off, cap, batch_token); if (st != ORBHIP_OK) return st;
+    *batch_token = 0; hit_off[0] = 0;
+    if (nq == 0) return ORBHIP_OK;
+    if (!bow_off || bow_off[0] < 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lock(db->m);
+    st = kf_batch_room(db, nq); if (st != ORBHIP_OK) return st;
+    for (int i = 0; i < nq; i++) {
+        const long long n = (long long)bow_off[i + 1] - bow_off[i];
+        if (n < 0 || (n > 0 && (!bow_id || !bow_val))) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+        if (n > KFDB_MAX_WORDS) return orbhip_set_error(ORBHIP_ERR_UNSUPPORTED, "query %d: a BowVector of %lld words (at most %d)", i, n, KFDB_MAX_WORDS);
+        if (!kf_ascending(bow_id + bow_off[i], (int)n, db->nwords)) return orbhip_set_error(ORBHIP_ERR_INVALID, "query %d: BowVector ids must ascend and lie below %d", i, db->nwords);
+    }
+    KFCHK(hipSetDevice(db->device));
+    hipStream_t s = orbhip_thread_stream(db->device);
+    KfBatch* B = db->batch;
+    const size_t b0 = (size_t)bow_off[0], nb = (size_t)bow_off[nq] - b0;
+    std::vector<KfBq> bq((size_t)nq);
+    for (int i = 0; i < nq; i++) { bq[i].id_off = (long long)((size_t)bow_off[i] - b0) * 4; bq[i].val_off = (long long)((size_t)bow_off[i] - b0) * 8; bq[i].n = bow_off[i + 1] - bow_off[i]; bq[i].pad = 0; }
+    KFCHK(kf_grow(&B->d_qid, &B->qid_cap, std::max<size_t>(nb, 1))); KFCHK(kf_grow(&B->d_qval, &B->qval_cap, std::max<size_t>(nb, 1)));
+    if (nb > 0) {
+        KFCHK(hipMemcpyAsync(B->d_qid, bow_id + b0, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        KFCHK(hipMemcpyAsync(B->d_qval, bow_val + b0, nb * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    return kf_batch_core(db, kind, nq, qids, B->d_qid, B->d_qval, bq, excl_off, excl_slot, min_score, hit_off, nsharing, min_common, hits, cap, batch_token, s);
+}
+
+extern "C" orbhip_status orbhip_kfdb_query_frames(orbhip_kfdb* db, int kind, const uint64_t* qids, orbhip_ctx* ctx, orbhip_voc* voc, int first_frame, int nq,
+                                                  const int32_t* excl_off, const int32_t* excl_slot, const float* min_score,
+                                                  int32_t* hit_off, int32_t* nsharing, int32_t* min_common, orbhip_kfdb_hit* hits, int cap, uint64_t* batch_token)
+{
+    OrbApiTimer api_timer;
+    orbhip_status st = kf_batch_args(db, kind, nq, qids, excl_off, excl_slot, min_score, hit_off, cap, batch_token); if (st != ORBHIP_OK) return st;
+    if (!ctx || !voc) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    *batch_token = 0; hit_off[0] = 0;
+    if (nq == 0) return ORBHIP_OK;
+    const uint32_t* d_id0 = nullptr; const double* d_val0 = nullptr; const int* d_n0 = nullptr; int qcap = 0, device = 0, nwords = 0; hipStream_t s = nullptr;
+    std::vector<KfBq> bq((size_t)nq);
+    long long n_pitch = 0;
+    for (int i = 0; i < nq; i++) {
+        const uint32_t* d_id = nullptr; const double* d_val = nullptr; const int* d_n = nullptr;
+        st = orbhip_bow_resident(ctx, voc, first_frame + i, &d_id, &d_val, &d_n, &qcap, &device, &nwords, &s); if (st != ORBHIP_OK) return st;
+        if (i == 0) { d_id0 = d_id; d_val0 = d_val; d_n0 = d_n; }
+        bq[i].id_off = reinterpret_cast<const char*>(d_id) - reinterpret_cast<const char*>(d_id0); bq[i].val_off = reinterpret_cast<const char*>(d_val) - reinterpret_cast<const char*>(d_val0);
+        bq[i].n = 0; bq[i].pad = 0;
+        if (i == 1) n_pitch = reinterpret_cast<const char*>(d_n) - reinterpret_cast<const char*>(d_n0);
+    }
+    if (device != db->device || nwords != db->nwords) return orbhip_set_error(ORBHIP_ERR_INVALID, "database for %d words on device %d, vocabulary of %d words on device %d", db->nwords, db->device, nwords, device);
+    std::lock_guard<std::mutex> lock(db->m);
+    st = kf_batch_room(db, nq); if (st != ORBHIP_OK) return st;
+    KFCHK(hipSetDevice(db->device));
+    std::vector<int> lens((size_t)nq, 0);                                 // the tiles are planned on the host: one download of nq lengths, no BowVector travels
+    KFCHK(hipMemcpy2DAsync(lens.data(), sizeof(int), d_n0, nq > 1 ? (size_t)n_pitch : sizeof(int), sizeof(int), (size_t)nq, hipMemcpyDeviceToHost, s));
+    KFCHK(hipStreamSynchronize(s));
+    for (int i = 0; i < nq; i++) bq[i].n = std::max(0, std::min(lens[i], std::min(qcap, KFDB_MAX_WORDS)));
+    return kf_batch_core(db, kind, nq, qids, d_id0, d_val0, bq, excl_off, excl_slot, min_score, hit_off, nsharing, min_common, hits, cap, batch_token, s);     // on the extractor's stream: behind orbhip_compute_bow
+}
+
+static orbhip_status kf_batch_token(orbhip_kfdb* db, uint64_t token)      // the lock held
+{
+    if (!db->batch || !db->batch->valid || db->batch->token != token || token == 0)
+        return orbhip_set_error(ORBHIP_ERR_INVALID, "key-frame database: batch token %llu is superseded (a later query or clear) or was never given", (unsigned long long)token);
+    return ORBHIP_OK;
+}
+
+extern "C" orbhip_status orbhip_kfdb_batch_hits(orbhip_kfdb* db, uint64_t batch_token, int first_query, int nqueries, orbhip_kfdb_hit* hits, int cap)
+{
+    OrbApiTimer api_timer;
+    if (!db || first_query < 0 || nqueries < 0 || cap < 0 || (cap > 0 && !hits)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::lock_guard<std::mutex> lock(db->m);
+    const orbhip_status st = kf_batch_token(db, batch_token); if (st != ORBHIP_OK) return st;
+    KfBatch* B = db->batch;
+    if ((long long)first_query + nqueries > B->nq) return orbhip_set_error(ORBHIP_ERR_INVALID, "queries %d..%d of a batch of %d", first_query, first_query + nqueries, B->nq);
+    const int o = B->hit_off[first_query], n = B->hit_off[first_query + nqueries] - o;
+    if (n > cap) return orbhip_set_error(ORBHIP_ERR_CAPACITY, "key-frame database: %d hits, room for %d", n, cap);
+    if (n == 0) return ORBHIP_OK;
+    KFCHK(hipSetDevice(db->device));
+    hipStream_t s = orbhip_thread_stream(db->device);
+    KFCHK(hipMemcpyAsync(hits, B->d_hits + o, (size_t)n * sizeof(orbhip_kfdb_hit), hipMemcpyDeviceToHost, s));
+    KFCHK(hipStreamSynchronize(s));
+    return ORBHIP_OK;
+}
+
+// orbhip_kfdb_select for every query of the batch, each over the states its neighbours had right after that query (the snapshot)
+extern "C" orbhip_status orbhip_kfdb_select_batch(orbhip_kfdb* db, uint64_t batch_token, int kind, const orbhip_kfdb_hit* hits, const int32_t* hit_off,
+                                                  const int32_t* neigh_off, const int32_t* neigh_slot, int32_t* out_slots, int32_t* out_off, int cap)
+{
+    OrbApiTimer api_timer;
+    if (!db || !hit_off || !out_off || cap < 0 || (kind != ORBHIP_KFDB_RELOC && kind != ORBHIP_KFDB_LOOP) || (cap > 0 && !out_slots)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+    std::vector<int> list; std::vector<KfState> ns; std::vector<unsigned long long> qid; std::vector<float> min_score; std::vector<int> min_common;
+    int nq = 0, nslots = 0, nh = 0;
+    {
+        std::lock_guard<std::mutex> lock(db->m);
+        const orbhip_status st = kf_batch_token(db, batch_token); if (st != ORBHIP_OK) return st;
+        KfBatch* B = db->batch;
+        if (kind != B->kind) return orbhip_set_error(ORBHIP_ERR_INVALID, "the batch was of kind %d", B->kind);
+        nq = B->nq; nslots = db->nslots; qid = B->qid; min_score = B->min_score; min_common = B->min_common;
+        if (hit_off[0] != 0) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad hit offsets");
+        for (int i = 0; i < nq; i++) if (hit_off[i + 1] < hit_off[i]) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad hit offsets");
+        nh = hit_off[nq];
+        if (nh > 0 && (!hits || !neigh_off)) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad argument");
+        const int nn = nh > 0 ? neigh_off[nh] : 0;
+        if (nh > 0 && (neigh_off[0] != 0 || nn < 0 || (nn > 0 && !neigh_slot))) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad neighbour lists");
+        for (int i = 0; i < nh; i++) {
+            if (neigh_off[i + 1] < neigh_off[i]) return orbhip_set_error(ORBHIP_ERR_INVALID, "bad neighbour lists");
+            if (hits[i].slot < 0 || hits[i].slot >= nslots) return orbhip_set_error(ORBHIP_ERR_INVALID, "hit %d names slot %d", i, hits[i].slot);
+        }
+        list.resize((size_t)nn); ns.resize((size_t)nn);
+        std::vector<long long> cell((size_t)nn);
+        for (int q = 0; q < nq; q++)
+            for (int i = hit_off[q]; i < hit_off[q + 1]; i++)
+                for (int j = neigh_off[i]; j < neigh_off[i + 1]; j++) {
+                    const int sl = neigh_slot[j];
+                    list[j] = kf_live(db, sl) ? sl : -1;                                          // liveness as it is now, as orbhip_kfdb_select reads it
+                    // a key frame added since the batch was never met by it: the zero state of a new slot
+                    cell[j] = (list[j] >= 0 && sl < B->nslots && db->h_slots[sl].seq < B->next_seq) ? (long long)((size_t)q * B->stride + (size_t)sl) : -1;
+                }
+        if (nn > 0) {
+            KFCHK(hipSetDevice(db->device));
+            hipStream_t s = orbhip_thread_stream(db->device);
+            KFCHK(kf_grow(&B->d_cells, &B->cells_cap, (size_t)nn)); KFCHK(kf_grow(&B->d_gather, &B->gather_cap, (size_t)nn));
+            KFCHK(hipMemcpyAsync(B->d_cells, cell.data(), (size_t)nn * sizeof(long long), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_kfdb_gather_batch, dim3((nn + 255) / 256, 1, 1), dim3(256, 1, 1), 0, s, B->d_swords, B->d_sscore, B->d_smatch, B->d_cells, nn, B->d_gather);
+            KFCHK(hipGetLastError());
+            KFCHK(hipMemcpyAsync(ns.data(), B->d_gather, (size_t)nn * sizeof(KfState), hipMemcpyDeviceToHost, s));
+            KFCHK(hipStreamSynchronize(s));
+        }
+        for (int q = 0; q < nq; q++)
+            for (int i = hit_off[q]; i < hit_off[q + 1]; i++)
+                for (int j = neigh_off[i]; j < neigh_off[i + 1]; j++) {
+                    if (cell[j] < 0) ns[j].query = 0; else ns[j].query = ns[j].query ? qid[q] : ~qid[q];      // (a new slot's query field is 0)
+                }
+    }
+    std::vector<int> picked; int total = 0; bool fits = true;
+    out_off[0] = 0;
+    for (int q = 0; q < nq; q++) {
+        const int h0 = hit_off[q], n = hit_off[q + 1] - h0;
+        picked.clear();
+        if (n > 0) kf_select_host(kind, qid[q], min_common[q], min_score[q], hits + h0, n, neigh_off + h0, list.data(), ns.data(), nslots, picked);
+        if ((long long)total + (long long)picked.size() > cap) fits = false;
+        if (fits) for (size_t i = 0; i < picked.size(); i++) out_slots[total + (int)i] = picked[i];
+        total += (int)picked.size(); out_off[q + 1] = total;
+    }
+    if (!fits) return orbhip_set_error(ORBHIP_ERR_CAPACITY, "key-frame database: %d candidates, room for %d", total, cap);
     return ORBHIP_OK;
 }

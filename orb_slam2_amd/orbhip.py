@@ -41,7 +41,8 @@ SYMBOLS = [
     "orbhip_device_synchronize", "orbhip_submit_to",
     "orbhip_predict_scale_table", "orbhip_project_search_bounds", "orbhip_project_search_frame", "orbhip_project_best_in_window_bounds", "orbhip_project_best_in_window_batch", "orbhip_project_best_in_window_shared", "orbhip_project_best_in_window_held",
     "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_clear", "orbhip_kfdb_size", "orbhip_kfdb_add", "orbhip_kfdb_erase", "orbhip_kfdb_query", "orbhip_kfdb_query_frame",
-    "orbhip_kfdb_state", "orbhip_kfdb_scores", "orbhip_kfdb_select", "orbhip_kfdb_set_scoring", "orbhip_kfdb_get_scoring", "orbhip_voc_set_scoring",
+    "orbhip_kfdb_state", "orbhip_kfdb_scores", "orbhip_kfdb_select", "orbhip_kfdb_set_scoring", "orbhip_kfdb_get_scoring",
+    "orbhip_kfdb_query_batch", "orbhip_kfdb_query_frames", "orbhip_kfdb_batch_hits", "orbhip_kfdb_select_batch", "orbhip_voc_set_scoring",
     "orbhip_voc_create", "orbhip_voc_save_text", "orbhip_voc_create_level_ms",
 ]
 
@@ -254,6 +255,10 @@ def lib(path=None):
     L.orbhip_kfdb_select.argtypes = [vp, C.c_int, C.c_uint64, C.c_int, C.c_float, vp, C.c_int, vp, vp, vp, C.c_int, ip]
     L.orbhip_kfdb_set_scoring.argtypes = [vp, C.c_int]
     L.orbhip_kfdb_get_scoring.argtypes = [vp]
+    L.orbhip_kfdb_query_batch.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, u64p]
+    L.orbhip_kfdb_query_frames.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, u64p]
+    L.orbhip_kfdb_batch_hits.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, vp, C.c_int]
+    L.orbhip_kfdb_select_batch.argtypes = [vp, C.c_uint64, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]
     L.orbhip_voc_set_scoring.argtypes = [vp, C.c_int]
     _libs[path] = L
     return L
@@ -1175,6 +1180,71 @@ class KeyFrameDatabase:
         _check(self.L_.orbhip_kfdb_select(self.h, kind, int(qid), int(min_common), min_score, _p(hits), len(hits), _p(off), _p(flat), _p(out), cap, C.byref(n)),
                "orbhip_kfdb_select", self.L_)
         return out[:n.value].copy()
+
+    # ---- batched queries: nq queries of one kind answered in order by one call (orbhip_kfdb_query_batch)
+    def _batch(self, what, kind, qids, excluded, min_score, call):
+        qids = np.ascontiguousarray(qids, np.uint64)
+        nq = len(qids)
+        excluded = [[] for _ in range(nq)] if excluded is None else excluded
+        eoff = np.zeros(nq + 1, np.int32)
+        eoff[1:] = np.cumsum([len(e) for e in excluded], dtype=np.int64)
+        eflat = np.ascontiguousarray(np.concatenate([np.asarray(e, np.int32).reshape(-1) for e in excluded]) if nq else [], np.int32)
+        ms = np.ascontiguousarray(np.zeros(nq) if min_score is None else np.broadcast_to(min_score, (nq,)), np.float32)
+        hit_off, nsh, mc = np.zeros(nq + 1, np.int32), np.zeros(max(nq, 1), np.int32), np.zeros(max(nq, 1), np.int32)
+        token = C.c_uint64(0)
+        cap = int(min(nq * max(len(self), 1), 1 << 16))                   # room for most batches' hits in the same call; a larger list is fetched afterwards
+        hits = np.zeros(max(cap, 1), KFDB_HIT)
+        st = call(nq, _p(qids), _p(eoff), _p(eflat), _p(ms), _p(hit_off), _p(nsh), _p(mc), _p(hits), cap, C.byref(token))
+        if st == ERR_CAPACITY:
+            hits = np.zeros(int(hit_off[nq]), KFDB_HIT)
+            _check(self.L_.orbhip_kfdb_batch_hits(self.h, token.value, 0, nq, _p(hits), int(hit_off[nq])), "orbhip_kfdb_batch_hits", self.L_)
+        else:
+            _check(st, what, self.L_)
+        return KfdbBatch(token.value, kind, qids, hits[:hit_off[nq]].copy(), hit_off, nsh[:nq].copy(), mc[:nq].copy())
+
+    def query_batch(self, kind, qids, bows, excluded=None, min_score=None):
+        """bows[i] = (ids, values) of query i; excluded[i] its excluded slots and min_score (a number or one per query) its minScore, LOOP only.
+        -> KfdbBatch: what `query` returns for the same queries issued in this order, and the token `select_batch` takes"""
+        bows = [self._bow(*b) for b in bows]
+        boff = np.zeros(len(bows) + 1, np.int32)
+        boff[1:] = np.cumsum([len(b[0]) for b in bows], dtype=np.int64)
+        bid = np.ascontiguousarray(np.concatenate([b[0] for b in bows]) if bows else [], np.uint32)
+        bval = np.ascontiguousarray(np.concatenate([b[1] for b in bows]) if bows else [], np.float64)
+        if len(bows) != len(qids):
+            raise ValueError("one BowVector per query id")
+        return self._batch("orbhip_kfdb_query_batch", kind, qids, excluded, min_score, lambda nq, q, eo, ef, ms, ho, ns, mc, hits, cap, tok: self.L_.orbhip_kfdb_query_batch(
+            self.h, kind, nq, q, _p(boff), _p(bid), _p(bval), eo, ef, ms, ho, ns, mc, hits, cap, tok))
+
+    def query_frames(self, kind, qids, extractor, voc, first_frame=0, excluded=None, min_score=None):
+        """`query_batch` with query i read where voc.compute_bow(extractor, ...) left frame first_frame + i on the device"""
+        return self._batch("orbhip_kfdb_query_frames", kind, qids, excluded, min_score, lambda nq, q, eo, ef, ms, ho, ns, mc, hits, cap, tok: self.L_.orbhip_kfdb_query_frames(
+            self.h, kind, q, extractor.h, voc.h, int(first_frame), nq, eo, ef, ms, ho, ns, mc, hits, cap, tok))
+
+    def select_batch(self, batch, neighbours):
+        """neighbours[h] = the slots of GetBestCovisibilityKeyFrames(10) of batch.hits[h]'s key frame -> the candidate slots of every query"""
+        nh, nq = len(batch.hits), len(batch.qids)
+        off = np.zeros(nh + 1, np.int32)
+        off[1:] = np.cumsum([len(v) for v in neighbours], dtype=np.int64)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(v, np.int32).reshape(-1) for v in neighbours]) if nh else [], np.int32)
+        cap = 11 * nh + 1
+        out, out_off = np.zeros(cap, np.int32), np.zeros(nq + 1, np.int32)
+        hits = np.ascontiguousarray(batch.hits, KFDB_HIT)
+        _check(self.L_.orbhip_kfdb_select_batch(self.h, batch.token, batch.kind, _p(hits), _p(batch.hit_off), _p(off), _p(flat), _p(out), _p(out_off), cap),
+               "orbhip_kfdb_select_batch", self.L_)
+        return [out[out_off[i]:out_off[i + 1]].copy() for i in range(nq)]
+
+
+class KfdbBatch:
+    """What a batched query returned: hits (all queries, flat), hit_off[nq + 1], nsharing[nq], min_common[nq] and the token of its snapshot"""
+
+    def __init__(self, token, kind, qids, hits, hit_off, nsharing, min_common):
+        self.token, self.kind, self.qids, self.hits, self.hit_off, self.nsharing, self.min_common = token, kind, qids, hits, hit_off, nsharing, min_common
+
+    def __len__(self):
+        return len(self.qids)
+
+    def query_hits(self, i):
+        return self.hits[self.hit_off[i]:self.hit_off[i + 1]]
 
 
 def search_by_bow(mode, desc1, angle1, valid1, fv1, desc2, angle2, valid2, fv2, nnratio=0.7, check_ori=True, device=0, library=None):
