@@ -238,6 +238,31 @@ orbhip_status orbhip_hamming_nn_device_expanded(void* stream, const uint8_t* d_q
 orbhip_status orbhip_distinctive_descriptors(int device, const uint8_t* desc /* total x 32 */, const int32_t* offsets /* npoints + 1, non-decreasing, offsets[0] = 0 */,
                                              int npoints, int32_t* best_index /* npoints */, int32_t* best_median /* npoints, may be NULL */);
 
+/* Optimizer::PoseOptimization (Optimizer.cc:239-451): one SE(3) pose against n observed map points, as g2o runs it there - four rounds of at most ten
+   Levenberg-Marquardt iterations restarted from Tcw_in, Huber kernel in the first three, observations re-classified after each round (chi2 > 5.991
+   monocular, > 7.815 stereo, compared in float).  An observation is monocular where u_right < 0.  inv_sigma2 is mvInvLevelSigma2[octave]; (X, Y, Z) is
+   the map point's world position.  Inputs are float, every computation is double, Tcw_out is the estimate rounded to float (row-major 4 x 4, like
+   mTcw).  outlier[i] is mvbOutlier of observation i, *n_inliers the member's return value.  With n < 3 the call returns ORBHIP_OK with *n_inliers = 0
+   and writes neither Tcw_out nor outlier.  One launch per call, all problems of a batch in the same one; results repeat bit for bit and do not
+   depend on a problem's place in a batch.  Re-entrant like every entry on host arrays (the calling thread's own stream and arena). */
+typedef struct { float u, v, u_right /* < 0: monocular */, inv_sigma2, X, Y, Z; } orbhip_pose_obs;
+typedef struct { float fx, fy, cx, cy, bf; } orbhip_pose_camera;
+typedef struct {
+    orbhip_pose_camera cam; float Tcw_in[16]; const orbhip_pose_obs* obs; int32_t n;
+    float Tcw_out[16]; uint8_t* outlier /* n bytes */; int32_t n_inliers;
+} orbhip_pose_problem;
+orbhip_status orbhip_pose_optimization(int device, const orbhip_pose_camera* cam, const float* Tcw_in /* 16 */, const orbhip_pose_obs* obs, int n,
+                                       float* Tcw_out /* 16 */, uint8_t* outlier /* n */, int* n_inliers);
+/* independent problems of any mix of sizes (Tracking::Relocalization's candidates): one upload, one launch, one download */
+orbhip_status orbhip_pose_optimization_batch(int device, int nproblems, orbhip_pose_problem* problems);
+/* The same on a frame of the context's last extraction: observation i is key point idx[i] of that frame - u, v and octave of the UNDISTORTED key point
+   and its right column are read where they lie on the device (the columns of the last stereo / RGB-D step or of orbhip_set_stereo_columns; none: every
+   observation is monocular), inv_sigma2 comes from the context's own level table (orbhip_get_scale_tables) - against the point xyz[3i .. 3i+2].
+   Runs on the context's stream. */
+orbhip_status orbhip_pose_optimization_frame(orbhip_ctx* ctx, int frame, const orbhip_pose_camera* cam, const float* Tcw_in /* 16 */,
+                                             const int32_t* idx /* m */, const float* xyz /* 3 m */, int m,
+                                             float* Tcw_out /* 16 */, uint8_t* outlier /* m */, int* n_inliers);
+
 /* ORBmatcher(nnratio, check_ori).SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, window)
    (ORBmatcher.h:69, ORBmatcher.cc:405-520) on host buffers.  The Frame members it reads are passed flat:
    mvKeysUn / mDescriptors of both frames and the image bounds (mnMinX = mnMinY = 0, mnMaxX = im_w,

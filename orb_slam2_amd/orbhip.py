@@ -20,7 +20,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
 
 # every symbol include/orbhip.h declares (tests check the library exports all of them)
 SYMBOLS = [
-    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
+    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
     "orbhip_get_scale_tables", "orbhip_level_size", "orbhip_extract", "orbhip_extract_batch", "orbhip_pyramid_level",
     "orbhip_extract_device", "orbhip_sync", "orbhip_fetch", "orbhip_fetch_matches", "orbhip_descriptor_distance",
     "orbhip_hamming_nn", "orbhip_hamming_nn_device", "orbhip_nn_expanded_size", "orbhip_nn_expand_device", "orbhip_hamming_nn_device_expanded", "orbhip_search_for_initialization", "orbhip_profile_enable",
@@ -189,6 +189,9 @@ def lib(path=None):
     L.orbhip_descriptor_distance.argtypes = [vp, vp]
     L.orbhip_hamming_nn.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.orbhip_distinctive_descriptors.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp]
+    L.orbhip_pose_optimization.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.orbhip_pose_optimization_batch.argtypes = [C.c_int, C.c_int, vp]
+    L.orbhip_pose_optimization_frame.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.orbhip_hamming_nn_device.argtypes = [vp, vp, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.orbhip_nn_expanded_size.argtypes = [C.c_int64]; L.orbhip_nn_expanded_size.restype = C.c_size_t
     L.orbhip_nn_expand_device.argtypes = [vp, vp, C.c_int64, vp]
@@ -524,6 +527,21 @@ class ORBextractor:
         """mvuRight computed on the host (the reference's Frame::ComputeStereoFromRGBD loop) for a frame of the last call: the resident searches read it in HBM."""
         u = np.ascontiguousarray(u_right, np.float32)
         _check(self.L.orbhip_set_stereo_columns(self.h, frame, _p(u), len(u)), "orbhip_set_stereo_columns", self.L)
+
+    def pose_optimization_frame(self, cam, Tcw, idx, xyz, frame=0):
+        """Optimizer::PoseOptimization on a frame of the last call: observation i is undistorted key point idx[i] of that frame (its right column and
+        1 / sigma^2 read on the device) against the map point xyz[i].  cam = (fx, fy, cx, cy, bf).  Returns (Tcw, outlier, n_inliers); with fewer than
+        3 observations Tcw is the input and outlier is all zero."""
+        cam = np.ascontiguousarray(cam, np.float32).reshape(5)
+        Tin = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        if len(xyz) != len(idx):
+            raise ValueError("one point per index")
+        out, flags, ninl = Tin.copy(), np.zeros(len(idx), np.uint8), C.c_int(0)
+        _check(self.L.orbhip_pose_optimization_frame(self.h, frame, _p(cam), _p(Tin), _p(idx), _p(xyz), len(idx), _p(out), _p(flags), C.byref(ninl)),
+               "orbhip_pose_optimization_frame", self.L)
+        return out.reshape(4, 4), flags.astype(bool), ninl.value
 
     def mvImagePyramid(self, level, frame=0):
         w, h = self.level_size(level)
@@ -931,6 +949,54 @@ def distinctive_descriptors(desc, offsets, device=None, library=None):
     L = lib(library)
     _check(L.orbhip_distinctive_descriptors(0 if device is None else device, _p(desc), _p(offsets), n, _p(bi), _p(bm)), "orbhip_distinctive_descriptors", L)
     return bi, bm
+
+
+POSE_OBS_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("u_right", "<f4"), ("inv_sigma2", "<f4"), ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4")])     # orbhip_pose_obs
+
+
+class _PoseProblem(C.Structure):                                                # orbhip_pose_problem
+    _fields_ = [("cam", C.c_float * 5), ("Tcw_in", C.c_float * 16), ("obs", C.c_void_p), ("n", C.c_int32),
+                ("Tcw_out", C.c_float * 16), ("outlier", C.c_void_p), ("n_inliers", C.c_int32)]
+
+
+def _pose_obs(obs):
+    obs = np.asarray(obs)
+    return np.ascontiguousarray(obs if obs.dtype == POSE_OBS_DTYPE else np.ascontiguousarray(obs, np.float32).reshape(-1, 7).view(POSE_OBS_DTYPE).reshape(-1))
+
+
+def pose_optimization(cam, Tcw, obs, device=None, library=None):
+    """Optimizer::PoseOptimization: cam = (fx, fy, cx, cy, bf), Tcw the 4 x 4 initial pose, obs an array of POSE_OBS_DTYPE (or n x 7 float32:
+    u, v, u_right (< 0: monocular), inv_sigma2, X, Y, Z).  Returns (Tcw, outlier, n_inliers); with fewer than 3 observations nothing is computed:
+    Tcw is the input, outlier all zero, n_inliers 0."""
+    cam = np.ascontiguousarray(cam, np.float32).reshape(5)
+    Tin = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    obs = _pose_obs(obs)
+    out, flags, ninl = Tin.copy(), np.zeros(len(obs), np.uint8), C.c_int(0)
+    L = lib(library)
+    _check(L.orbhip_pose_optimization(0 if device is None else device, _p(cam), _p(Tin), _p(obs), len(obs), _p(out), _p(flags), C.byref(ninl)), "orbhip_pose_optimization", L)
+    return out.reshape(4, 4), flags.astype(bool), ninl.value
+
+
+def pose_optimization_batch(problems, device=None, library=None):
+    """Independent pose optimisations in one device call: problems is a sequence of (cam, Tcw, obs) as pose_optimization takes them.
+    Returns a list of (Tcw, outlier, n_inliers)."""
+    n = len(problems)
+    arr = (_PoseProblem * max(n, 1))()
+    keep = []
+    for k, (cam, Tcw, obs) in enumerate(problems):
+        obs = _pose_obs(obs)
+        flags = np.zeros(len(obs), np.uint8)
+        keep.append((obs, flags))
+        Tin = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        arr[k].cam[:] = [float(v) for v in np.ascontiguousarray(cam, np.float32).reshape(5)]
+        arr[k].Tcw_in[:] = [float(v) for v in Tin]
+        arr[k].Tcw_out[:] = [float(v) for v in Tin]
+        arr[k].obs = obs.ctypes.data if len(obs) else None
+        arr[k].n = len(obs)
+        arr[k].outlier = flags.ctypes.data if len(obs) else None
+    L = lib(library)
+    _check(L.orbhip_pose_optimization_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_pose_optimization_batch", L)
+    return [(np.array(arr[k].Tcw_out[:], np.float32).reshape(4, 4), keep[k][1].astype(bool), int(arr[k].n_inliers)) for k in range(n)]
 
 
 def nn_expanded_size(ndb, library=None):
