@@ -352,12 +352,13 @@ extern "C" orbhip_status orbhip_create(orbhip_ctx** out, const orbhip_config* cf
     }
     // ---- per level geometry (ORBextractor.cc:1111-1112, 773-806, 543-545)
     c->geom.resize(L);
-    long long plane_off = 0, cand_off = 0; int kp_off = 0;
+    long long plane_off = 0, blur_off = 0, cand_off = 0; int kp_off = 0;
     for (int l = 0; l < L; l++) {
         LevelGeom& g = c->geom[l]; memset(&g, 0, sizeof g);
         g.w = cvRoundF((float)cfg->width * c->isf[l]); g.h = cvRoundF((float)cfg->height * c->isf[l]);
         if (g.w < 32 + 30 || g.h < 32 + 30 || g.w > 4095 || g.h > 4095) { const int gw = g.w, gh = g.h; delete c; return fail(ORBHIP_ERR_UNSUPPORTED, "level %d is %dx%d: supported level sizes are 62..4095 px per side (the reference divides by zero below 30 px of interior)", l, gw, gh); }
         g.pitch = (g.w + 63) & ~63; g.plane_off = (int)plane_off; plane_off += (long long)g.pitch * g.h;
+        g.blur_tpr = orbhip_blur_tiles_per_row(g.w); g.blur_off = (int)blur_off; blur_off += (long long)g.blur_tpr * orbhip_blur_tile_rows(g.h) * ORBHIP_BT_BYTES;     // the blurred level as 32x4 tiles
         g.maxBorderX = g.w - ORBHIP_EDGE; g.maxBorderY = g.h - ORBHIP_EDGE;
         const float width = (float)(g.maxBorderX - ORBHIP_EDGE), height = (float)(g.maxBorderY - ORBHIP_EDGE), W = 30;
         g.nCols = (int)(width / W); g.nRows = (int)(height / W);
@@ -430,7 +431,7 @@ extern "C" orbhip_status orbhip_create(orbhip_ctx** out, const orbhip_config* cf
             if (g.w < 8) c->blur_strip_ok = false;      // (its border patch reads the row's last eight columns from the staged tile)
         }
     }
-    c->plane_frame_bytes = (plane_off + 255) & ~255LL; c->cand_slots_per_frame = cand_off; c->qt_per_frame = cand_off;
+    c->plane_frame_bytes = (plane_off + 255) & ~255LL; c->blur_frame_bytes = (blur_off + 255) & ~255LL; c->cand_slots_per_frame = cand_off; c->qt_per_frame = cand_off;
     c->lvl_kp_per_frame = kp_off; c->out_cap = kp_off; c->lvl0_cap = c->geom[0].kp_cap;
     if (cand_off >= (1 << 24)) { delete c; return fail(ORBHIP_ERR_UNSUPPORTED, "too many candidate slots"); }
     if (orbhip_quadtree_lds_bytes(c->qt_maxn, c->qt_maxcells) > 150 * 1024) { const int qn = c->qt_maxn; delete c; return fail(ORBHIP_ERR_UNSUPPORTED, "nfeatures too large for the LDS quadtree (%d nodes)", qn); }
@@ -506,7 +507,7 @@ extern "C" orbhip_status orbhip_create(orbhip_ctx** out, const orbhip_config* cf
         }
         TRY(upload(&c->d_fc_dma, tab));
     }
-    TRY(dalloc(&c->d_pyr, B * c->plane_frame_bytes + 256)); TRY(dalloc(&c->d_blur, B * c->plane_frame_bytes + 256));
+    TRY(dalloc(&c->d_pyr, B * c->plane_frame_bytes + 256)); TRY(dalloc(&c->d_blur, B * c->blur_frame_bytes + 256));
     TRY(dalloc(&c->d_cell_count, B * c->cells.size())); TRY(dalloc(&c->d_cell_cand, B * c->cand_slots_per_frame));
     TRY(dalloc(&c->d_qt_val, B * c->qt_per_frame)); TRY(dalloc(&c->d_qt_code, B * c->qt_per_frame)); TRY(dalloc(&c->d_qt_node, B * c->qt_per_frame));
     TRY(dalloc(&c->d_lvl_kp, B * c->lvl_kp_per_frame));
@@ -563,7 +564,7 @@ ExtractParams make_params(orbhip_ctx* c, const uint8_t* d_img0, long long frame_
     ExtractParams P; memset(&P, 0, sizeof P);
     P.geom = c->d_geom; P.nlevels = c->L;
     P.img0 = d_img0; P.img0_frame_stride = frame_stride; P.img0_pitch = row_stride;
-    P.pyr = c->d_pyr; P.blur = c->d_blur; P.plane_frame_bytes = c->plane_frame_bytes;
+    P.pyr = c->d_pyr; P.blur = c->d_blur; P.plane_frame_bytes = c->plane_frame_bytes; P.blur_frame_bytes = c->blur_frame_bytes;
     P.cells = c->d_cells; P.ncells_total = (int)c->cells.size();
     P.cell_count = c->d_cell_count; P.cell_cand = c->d_cell_cand; P.cand_slots_per_frame = c->cand_slots_per_frame;
     P.qt_val = c->d_qt_val; P.qt_code = c->d_qt_code; P.qt_node = c->d_qt_node; P.qt_per_frame = c->qt_per_frame;
@@ -609,7 +610,7 @@ orbhip_status pipeline_frames(orbhip_ctx* c, ExtractParams& P, int f0, int nf, h
         { ProfScope ps(c, K_BLUR, bs); orbhip_launch_blur(P, c->gk, nf, bs); }
         HIPCHK(hipEventRecord(c->ev_blur, bs));
         HIPCHK(hipStreamWaitEvent(s, c->ev_blur, 0));
-    } else if (nf <= 8 && P.blur_band && !c->serial && orbhip_quadtree_lds_bytes(c->qt_maxn, c->qt_maxcells) + 18 * 1024 <= 160 * 1024) {        // (the blur's tile is static LDS beside the quadtree's dynamic block)
+    } else if (nf <= 8 && P.blur_band && !c->serial && orbhip_quadtree_lds_bytes(c->qt_maxn, c->qt_maxcells) + orbhip_blur_quadtree_static_lds() <= 160 * 1024) {        // (the blur's tile is static LDS beside the quadtree's dynamic block)
         // a handful of frames: one launch for both (the quadtree's few long workgroups beside the blur's tiles); its time is booked on the quadtree
         ProfScope ps(c, K_QUADTREE, s); orbhip_launch_blur_quadtree(P, nf, s);
     } else {

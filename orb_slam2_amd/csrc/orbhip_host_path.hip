@@ -569,7 +569,14 @@ extern "C" orbhip_status orbhip_debug_blurred_level(orbhip_ctx* c, int frame, in
 {
     if (!c || !dst || level < 0 || level >= c->L || frame < 0 || frame >= c->last_nimg) return fail(ORBHIP_ERR_INVALID, "bad argument");
     const LevelGeom& g = c->geom[level];
-    return copy_plane(c, c->d_blur + (size_t)frame * c->plane_frame_bytes + g.plane_off, g.pitch, g.w, g.h, dst, dst_stride);
+    // the blurred level is stored as 32x4 tiles (orbhip_blur_tile_addr): fetched whole and put back into rows here, the caller sees a row-major image
+    orbhip_status st = orbhip_sync(c); if (st != ORBHIP_OK) return st;
+    std::vector<uint8_t> tiled((size_t)g.blur_tpr * orbhip_blur_tile_rows(g.h) * ORBHIP_BT_BYTES);
+    HIPCHK(hipMemcpyAsync(tiled.data(), c->d_blur + (size_t)frame * c->blur_frame_bytes + g.blur_off, tiled.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int y = 0; y < g.h; y++)
+        for (int x = 0; x < g.w; x++) dst[(size_t)y * dst_stride + x] = tiled[orbhip_blur_tile_addr((unsigned)x, (unsigned)y, (unsigned)g.blur_tpr)];
+    return ORBHIP_OK;
 }
 extern "C" orbhip_status orbhip_debug_candidates(orbhip_ctx* c, int frame, int level, int32_t* xys, int cap, int* n_out)
 {

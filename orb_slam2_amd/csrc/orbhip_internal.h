@@ -1,9 +1,11 @@
 // orbhip_internal.h — layouts shared by the host orchestration (orbhip_api.hip, orbhip_host_path.hip, orbhip_search.hip, orbhip_frame.hip; their own header: orbhip_ctx.h) and the gfx950 kernels.
 //
 // HBM layout of one context (fixed W x H, B = max_batch camera slots); all arrays are [frame][...]:
-//   planes      u8   per frame: levels 0..L-1, level l at plane_off[l], row pitch[l] (multiple of 64 B).
-//               Two plane sets: pyramid (its level-0 slot is only used by the host-image API; the device API
-//               reads level 0 straight from the caller's buffer) and blurred.  FAST scores never reach HBM:
+//   planes      u8   per frame: levels 0..L-1, level l at plane_off[l], row pitch[l] (multiple of 64 B): the pyramid (its level-0
+//               slot is only used by the host-image API; the device API reads level 0 straight from the caller's buffer).
+//   blurred     u8   per frame (stride blur_frame_bytes): level l at blur_off[l] as 32-column x 4-row TILES of 128 bytes, one aligned
+//               cache line each, blur_tpr[l] tiles per tile row (orbhip_blur_tile_addr below).  Written by the three blur kernels, read by
+//               k_describe and orbhip_debug_blurred_level alone.  FAST scores never reach HBM:
 //               one wavefront per grid cell computes, suppresses and emits them from LDS.
 //   cell_count  i32  per frame: one counter per FAST grid cell of every level
 //   cell_cand   u32  per frame: per-cell candidate slots (cand_idx + rank), packed x | y<<12 | score<<24 in
@@ -41,8 +43,23 @@ inline hipError_t orbhip_dmalloc(void** p, size_t bytes)
 #define ORBHIP_TH_LOW 50            // ORBmatcher.cc:38
 #define ORBHIP_EDGE 16              // minBorder = EDGE_THRESHOLD-3 (ORBextractor.cc:773)
 
+// The blurred planes' layout, in one place: byte (x, y) of a level sits at tile (x >> 5, y >> 2), row y & 3 of the tile, byte x & 31 of that row
+#define ORBHIP_BT_W 32              // tile columns
+#define ORBHIP_BT_H 4               // tile rows
+#define ORBHIP_BT_BYTES (ORBHIP_BT_W * ORBHIP_BT_H)
+__host__ __device__ inline unsigned orbhip_blur_tile_addr(unsigned x, unsigned y, unsigned tiles_per_row)
+{
+    return ((y >> 2) * tiles_per_row + (x >> 5)) * (unsigned)ORBHIP_BT_BYTES + (y & 3u) * (unsigned)ORBHIP_BT_W + (x & 31u);
+}
+// tiles per tile row / tile rows of a w x h level.  ceil(w / 32) columns hold every 64-byte span k_describe stages: a key point has 18 <= cx,
+// cx + 18 < w, so the span from (cx - 18) & ~31 ends in the tile of column cx + 18 at the latest, and the span from (cx - 18) & ~15 - taken
+// when (cx - 18) & 31 > 27 - ends in the tile of column cx - 18 + 36; ceil(h / 4) rows hold the ten tile rows from (cy - 18) >> 2 likewise.
+__host__ __device__ inline int orbhip_blur_tiles_per_row(int w) { return (w + ORBHIP_BT_W - 1) / ORBHIP_BT_W; }
+__host__ __device__ inline int orbhip_blur_tile_rows(int h) { return (h + ORBHIP_BT_H - 1) / ORBHIP_BT_H; }
+
 struct LevelGeom {
     int w, h, pitch, plane_off;                 // level image
+    int blur_off, blur_tpr;                     // blurred level: byte offset in the frame's blurred planes, tiles per tile row
     int nCols, nRows, wCell, hCell;             // FAST grid (ORBextractor.cc:781-787)
     int maxBorderX, maxBorderY;                 // cols-16, rows-16 (ORBextractor.cc:775-776)
     int cell_first, ncells;                     // index range in the CellDesc table
@@ -76,7 +93,7 @@ struct ExtractParams {
     const LevelGeom* geom; int nlevels;
     int frame0, nframes;                                                   // first frame (camera slot) and frame count of this launch group
     const uint8_t* img0; long long img0_frame_stride; int img0_pitch;      // level-0 source
-    uint8_t* pyr; uint8_t* blur; long long plane_frame_bytes;
+    uint8_t* pyr; uint8_t* blur; long long plane_frame_bytes, blur_frame_bytes;
     const CellDesc* cells; int ncells_total;
     int* cell_count; unsigned* cell_cand; long long cand_slots_per_frame;
     unsigned* qt_val; unsigned* qt_code; int* qt_node; long long qt_per_frame;
@@ -194,6 +211,7 @@ void orbhip_launch_fast_cells(const ExtractParams& P, int nframes, hipStream_t s
 void orbhip_launch_quadtree(const ExtractParams& P, int nframes, hipStream_t s);
 void orbhip_launch_describe(const ExtractParams& P, int nframes, hipStream_t s);
 size_t orbhip_quadtree_lds_bytes(int maxn, int maxcells);
+size_t orbhip_blur_quadtree_static_lds();      // static LDS of k_blur_quadtree (the blur's tile) beside that dynamic block
 int orbhip_quadtree_scr(int maxn, int maxcells);
 void* orbhip_nn_workspace(size_t bytes, hipStream_t s);
 // orbhip_collect with one destination per frame (NULL = not wanted): the pool scatters camera c's results straight to row c

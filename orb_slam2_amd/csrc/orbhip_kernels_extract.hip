@@ -663,7 +663,7 @@ __global__ __launch_bounds__(256) void k_blur(ExtractParams P, BlurK K)
 #pragma unroll
     for (int r = 0; r < 10; r++) { const float4 v = s_h[(4 * rg + r) * (BLUR_TW / 4) + q]; h[r][0] = v.x; h[r][1] = v.y; h[r][2] = v.z; h[r][3] = v.w; }
     const bool half_even = P.blur_round_mode == 1 && gx < (g.w & ~3);      // x86 SSE2 build of OpenCV: cvtps2dq on whole 4-column groups
-    uint8_t* dstbase = P.blur + (long long)frame * P.plane_frame_bytes + g.plane_off + gx;
+    uint8_t* dstbase = P.blur + (long long)frame * P.blur_frame_bytes + g.blur_off;       // 32x4 tiles: gx is a multiple of 4, the dword stays inside one tile row
     auto strip = [&](auto he) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
@@ -681,7 +681,7 @@ __global__ __launch_bounds__(256) void k_blur(ExtractParams P, BlurK K)
                 const float v = decltype(he)::value ? sum * (1.0f / 65536.0f) : __builtin_floorf(__builtin_fmaf(sum, 1.0f / 65536.0f, 0.5f));
                 out = __builtin_amdgcn_cvt_pk_u8_f32(v, (unsigned)k, out);
             }
-            *reinterpret_cast<unsigned*>(dstbase + (long long)gy * g.pitch) = out;   // pitch multiple of 64, gx of 4: pad bytes absorb the tail
+            *reinterpret_cast<unsigned*>(dstbase + orbhip_blur_tile_addr((unsigned)gx, (unsigned)gy, (unsigned)g.blur_tpr)) = out;   // the tile's pad columns absorb the tail
         }
     };
     if (half_even) strip(std::true_type{}); else strip(std::false_type{});
@@ -703,7 +703,8 @@ __global__ __launch_bounds__(256) void k_blur(ExtractParams P, BlurK K)
 //           (lane = its row i' = column, bytes = its k = source row) once each value is split into a low and a high byte plane
 //           (4 v_perm per 4 values); D2[i' = column][j' = output row] = sum_r VB[r][j'] * plane[r], for both planes, then
 //           2^8 D2hi + D2lo (+ constant) is the column filter's int32 sum; rounding, saturation and packing as in k_blur (v_cvt_pk_u8_f32);
-//   store:  D2 has lane = output row: the tile is transposed through LDS and leaves as whole rows (224 contiguous bytes per instruction).
+//   store:  D2 has lane = output row: the tile is transposed through LDS and leaves as whole 32x4 tiles of the blurred plane, two (256 contiguous
+//           bytes) per instruction (blur_store_tiles).
 // The band matrices (tap k - j - 1, zero elsewhere; VB also zero for the six incomplete output rows) come from a host table.  k is whatever
 // (lane half, byte) pair the hardware pairs between A and B: the kernel never needs the nominal k order (tools/mfma_probe.hip checks it).
 typedef int v4i __attribute__((vector_size(16)));
@@ -711,6 +712,9 @@ typedef int v2i __attribute__((vector_size(8)));
 typedef int v16i __attribute__((vector_size(64)));
 #define BM_IN_DW 68                     // dwords per staged source row: 64 loaded (columns x0 - 4 .. x0 + 251) + 4 of padding against bank conflicts
 #define BM_OUT_DW 57                    // dwords per row of the output tile in LDS (56 used)
+#define BM_OUT_PAD 2                    // the output tile's row r is row r + 2 in LDS: the tile rows of the blurred plane a 26-row tile touches start up to two rows
+#define BM_OUT_TAIL 8                   // dwords behind the last row: the store's fourth tile pair reads 64 dwords of a row
+#define BM_OUT_ROWS (BM_ROWS + 2 * BM_OUT_PAD)     // above it and end up to two rows below (blur_store_tiles reads those rows, in bounds, and stores none of them)
 // ---- k_blur_mfma in four steps (shared by the one-tile and the pipelined form of the kernel)
 struct BlurTile { TileDesc t; LevelGeom g; const uint8_t* src; int spitch; };
 __device__ __forceinline__ BlurTile blur_tile(const ExtractParams& P, int frame, int tile)
@@ -853,11 +857,47 @@ __device__ __forceinline__ void blur_blocks(int gw, int x0, int he_limit, const 
                         else v = gx < he_limit ? q : __builtin_floorf(q + 0.5f);
                         out = __builtin_amdgcn_cvt_pk_u8_f32(v, (unsigned)k, out);
                     }
-                    if (kSpelled) lds_write_b32(s_out + i * BM_OUT_DW + 8 * c + 2 * gq + h, out); else s_out[i * BM_OUT_DW + 8 * c + 2 * gq + h] = out;
+                    if (kSpelled) lds_write_b32(s_out + (i + BM_OUT_PAD) * BM_OUT_DW + 8 * c + 2 * gq + h, out); else s_out[(i + BM_OUT_PAD) * BM_OUT_DW + 8 * c + 2 * gq + h] = out;
                 }
             };
             if (all_he) finish(std::integral_constant<int, 1>{}); else if (none_he) finish(std::integral_constant<int, 0>{}); else finish(std::integral_constant<int, 2>{});
         }
+    }
+}
+// ---- store of an output tile (26 rows x up to 224 columns at (x0, y0) in s_out) into the blurred plane's 32x4 tiles (orbhip_blur_tile_addr): one
+// instruction writes TWO WHOLE TILES, 256 contiguous bytes - lane = (tile of the pair, row of the tile, dword of the row) is the lane's dword of those
+// bytes, so the global address is a scalar base + 4 lane.  x0 is a multiple of 224 = 7 tiles and y0 of 26, so y0 & 3 is 0 or 2: the 26 rows touch seven
+// tile rows, the last or the first of them by halves (two partial-line stores per tile column).  Wave w owns tile pair w of the strip - the fourth pair is
+// the seventh tile alone - and its k-th instruction is tile row k.  A wave whose pair lies past the image stores nothing; every other wave issues seven
+// stores for a tile whose 26 rows lie inside the image (blur_stores_per_wave: k_blur_strip counts them).
+__device__ __forceinline__ int blur_store_tiles_of(int gw, int x0) { return min(BM_BLOCKS, (gw - x0 + ORBHIP_BT_W - 1) / ORBHIP_BT_W); }
+__device__ __forceinline__ int blur_stores_per_wave(int ntiles, int wave) { return 2 * wave < ntiles ? 7 : 0; }
+template <bool kSpelled>
+__device__ __forceinline__ void blur_store_tiles(ORBHIP_GLOBAL uint8_t* dst, int tpr, int gw, int gh, int x0, int y0, int wave, int lane, const unsigned* s_out)
+{
+    static_assert(BM_ROWS == 26 && BM_COLS == ORBHIP_BT_W && ORBHIP_BT_H == 4 && BM_BLOCKS <= 8, "seven tile rows per output tile, one tile per 32-column block, a pair per wave");
+    // y0 is a multiple of BM_ROWS and BM_ROWS of 2, so y0 & 3 is 0 or 2: never above the pad (the LDS row tr + BM_OUT_PAD - (y0 & 3) stays >= 0), and the
+    // last tile row's last row, 4 * 6 + 3 - 0 + BM_OUT_PAD, stays inside the BM_OUT_ROWS rows
+    static_assert(BM_ROWS % 2 == 0 && BM_OUT_PAD >= 2 && 4 * 6 + 3 + BM_OUT_PAD < BM_OUT_ROWS, "the padded output tile holds every row the seven tile rows read");
+    const int ntiles = blur_store_tiles_of(gw, x0);
+    if (2 * wave >= ntiles) return;                                        // wave-uniform
+    const int tp = lane >> 5, tr = (lane >> 3) & 3, d = lane & 7, ya = y0 & 3;
+    // LDS row of tile row k's row tr: 4 k + tr - ya, shifted by BM_OUT_PAD (rows above the tile's first and below its last are read, in bounds, and not stored)
+    const unsigned* op = s_out + (tr + BM_OUT_PAD - ya) * BM_OUT_DW + 16 * wave + 8 * tp + d;      // (the fourth pair's second tile reads past the row's 56 dwords, at most BM_OUT_TAIL past the array's last row: never stored)
+    unsigned v[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++) v[k] = kSpelled ? lds_read_b32_issue(op + 4 * k * BM_OUT_DW) : op[4 * k * BM_OUT_DW];
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    if (kSpelled) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]));
+#endif
+    const bool colok = 2 * wave + tp < ntiles;
+    const int hi = min(BM_ROWS, gh - y0) + ya;                            // tile row k stores its rows tr with ya <= 4 k + tr < hi
+    const unsigned step = (unsigned)tpr * (unsigned)ORBHIP_BT_BYTES;
+    const unsigned tb = ((unsigned)(y0 >> 2) * (unsigned)tpr + (unsigned)(x0 >> 5) + 2u * (unsigned)wave) * (unsigned)ORBHIP_BT_BYTES;      // scalar; a frame's blurred planes are far below 2^32 bytes
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        const bool rowok = (k > 0 || tr >= ya) && tr < hi - 4 * k;
+        if (colok && rowok) *reinterpret_cast<ORBHIP_GLOBAL unsigned*>(dst + ((tb + (unsigned)k * step) + 4u * (unsigned)lane)) = v[k];      // scalar base, 32-bit lane offset
     }
 }
 __device__ __forceinline__ void blur_compute(const ExtractParams& P, const BlurTile& T, int wave, int lane, const unsigned* s_in, unsigned* s_out, const unsigned* s_band)
@@ -869,12 +909,8 @@ __device__ __forceinline__ void blur_compute(const ExtractParams& P, const BlurT
 __device__ __forceinline__ void blur_store(const ExtractParams& P, const BlurTile& T, int frame, int wave, int lane, const unsigned* s_out)
 {
     const LevelGeom& g = T.g; const int x0 = T.t.x0, y0 = T.t.y0;
-    // ---- store: wave w writes output rows w, w + 4, ..., lane = dword of the row (224 contiguous bytes per instruction)
-    uint8_t* dst = P.blur + (long long)frame * P.plane_frame_bytes + g.plane_off;
-    const int gx = x0 + 4 * lane;
-    if (lane < 8 * BM_BLOCKS && gx < g.w)
-        for (int r = wave; r < BM_ROWS && y0 + r < g.h; r += 4)
-            *reinterpret_cast<unsigned*>(dst + (long long)(y0 + r) * g.pitch + gx) = s_out[r * BM_OUT_DW + lane];      // pitch multiple of 64, gx of 4: pad bytes absorb the tail
+    // ---- store: whole tiles of the blurred plane, two per instruction (blur_store_tiles)
+    blur_store_tiles<false>(uniform_ptr(P.blur + (long long)frame * P.blur_frame_bytes + g.blur_off), g.blur_tpr, g.w, g.h, x0, y0, wave, lane, s_out);
 }
 
 // one tile of the matrix-core blur by the calling workgroup (256 threads): stage, patch, two banded products, round, store
@@ -896,7 +932,7 @@ __device__ __forceinline__ void blur_mfma_tile(const ExtractParams& P, int tile,
 __global__ __launch_bounds__(256, 5) void k_blur_mfma(ExtractParams P)
 {
     __shared__ __attribute__((aligned(16))) unsigned s_in[32 * BM_IN_DW];
-    __shared__ unsigned s_out[BM_ROWS * BM_OUT_DW];
+    __shared__ unsigned s_out[BM_OUT_ROWS * BM_OUT_DW + BM_OUT_TAIL];
     __shared__ __attribute__((aligned(16))) unsigned s_band[3 * 64 * 4];   // HB1 | HB2 | VB: fetched once per workgroup with coalesced 32-bit loads
     int tile, frame;                                                        // (as three 128-bit loads per lane they cost each wave 3 x 71 cycles of the texture addresser)
     if (!xcd_frame_map(P.nblur_tiles, P.nframes, tile, frame)) return;
@@ -913,11 +949,11 @@ __global__ __launch_bounds__(256, 5) void k_blur_mfma(ExtractParams P)
 //  * the border patch reads the staged tile, not memory: the lane whose dword starts at column w & ~3 (and every lane behind it) requests the four bytes
 //    that END at the row's end, columns w-4 .. w-1 - every column a reflected position of the patched dwords refers to lies in the last two whole dwords
 //    or in that one.  (Bytes of the patched dwords that no stored output reads may differ from blur_fix's: positions from w + 4 on.)
-//  * vmcnt: loads and stores of a wave complete in issue order.  Behind tile t's eight row requests the wave issues the stores of tile t - 1 (7 for waves
-//    0 and 1, 6 for waves 2 and 3: a tile that is followed by another has all its 26 rows inside the image) and the eight requests of tile t + 1, so
-//    "all but the newest 8 + stores" is tile t landed, without waiting for those stores.
+//  * vmcnt: loads and stores of a wave complete in issue order.  Behind tile t's eight row requests the wave issues the stores of tile t - 1 (seven two-tile
+//    stores, one per tile row, or none when the wave's tile pair lies past the image: blur_stores_per_wave; a tile that is followed by another has all its 26
+//    rows inside the image, so every one of the seven has active lanes) and the eight requests of tile t + 1, so "all but the newest 8 + stores" is tile t
+//    landed, without waiting for those stores.
 #define BS_NT 4                         // tiles per run: k_pyramid_level_g's choice for large batches and the one value measured (profiles/blur_strip_pipeline.txt)
-#define BS_OUT_ROWS 28                  // rows of the output tile in LDS (26 used; every wave reads seven rows w, w + 4, ...)
 __device__ __forceinline__ void blur_strip_issue(const ORBHIP_GLOBAL uint8_t* plane, unsigned spitch, int gh, unsigned coff, int y0, int wave, unsigned* s_in)
 {
 #pragma unroll
@@ -961,48 +997,30 @@ __device__ __forceinline__ void blur_strip_fix(int gw, int x0, bool fix_left, bo
 }
 struct BlurStrip {
     const ORBHIP_GLOBAL uint8_t* src; ORBHIP_GLOBAL uint8_t* dst;      // source plane, output plane of this frame
-    unsigned spitch, dpitch, coff; int gw, gh, x0, he_limit; bool fix_left, fix_right;
+    unsigned spitch, coff; int dtpr, gw, gh, x0, he_limit; bool fix_left, fix_right;      // dtpr: tiles per tile row of the output plane
 };
 // one tile of the run: y0 = its first row, `more` = another tile follows (its rows go to nxt), prev_stores = this wave's stores of the tile before
 __device__ __forceinline__ void blur_strip_step(const BlurStrip& S, int y0, bool more, int prev_stores, const v4i& HB1, const v4i& HB2, const v4i& VB,
                                                 int wave, int lane, unsigned* cur, unsigned* nxt, unsigned* s_out)
 {
-    if (more) {
-        blur_strip_issue(S.src, S.spitch, S.gh, S.coff, y0 + BM_ROWS, wave, nxt);
-        if (prev_stores == 0) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(8));
-        else if (prev_stores == 7) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(15));
-        else __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(14));
+    if (more) blur_strip_issue(S.src, S.spitch, S.gh, S.coff, y0 + BM_ROWS, wave, nxt);
+    if (more) {                                                        // prev_stores is 0 or 7 (blur_stores_per_wave)
+        if (prev_stores == 0) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(8)); else __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(15));
     } else {
-        if (prev_stores == 0) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(0));
-        else if (prev_stores == 7) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(7));
-        else __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(6));
+        if (prev_stores == 0) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(0)); else __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(7));
     }
     __builtin_amdgcn_wave_barrier();                                   // every lane's dwords have landed before any lane patches one
     blur_strip_fix(S.gw, S.x0, S.fix_left, S.fix_right, wave, lane, cur);
     lds_barrier_spelled();
     blur_blocks<true>(S.gw, S.x0, S.he_limit, HB1, HB2, VB, wave, lane, cur, s_out);
     lds_barrier_spelled();
-    // store: wave w writes output rows w, w + 4, ..., lane = dword of the row (224 contiguous bytes per instruction)
-    const unsigned* op = s_out + wave * BM_OUT_DW + min(lane, 8 * BM_BLOCKS - 1);
-    unsigned v[7];
-#pragma unroll
-    for (int k = 0; k < 7; k++) v[k] = lds_read_b32_issue(op + 4 * k * BM_OUT_DW);
-#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]));
-#endif
-    const int gx = S.x0 + 4 * lane;
-    if (lane < 8 * BM_BLOCKS && gx < S.gw) {
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-            const int r = wave + 4 * k;
-            if (r < BM_ROWS && y0 + r < S.gh) *reinterpret_cast<ORBHIP_GLOBAL unsigned*>(S.dst + ((unsigned)(y0 + r) * S.dpitch + (unsigned)gx)) = v[k];   // pitch multiple of 64, gx of 4: pad bytes absorb the tail
-        }
-    }
+    // store: whole tiles of the blurred plane, two per instruction
+    blur_store_tiles<true>(S.dst, S.dtpr, S.gw, S.gh, S.x0, y0, wave, lane, s_out);
 }
 __global__ __launch_bounds__(256, 5) void k_blur_strip(ExtractParams P)
 {
     __shared__ __attribute__((aligned(16))) unsigned s_in0[32 * BM_IN_DW], s_in1[32 * BM_IN_DW], s_band[3 * 64 * 4];
-    __shared__ unsigned s_out[BS_OUT_ROWS * BM_OUT_DW];
+    __shared__ unsigned s_out[BM_OUT_ROWS * BM_OUT_DW + BM_OUT_TAIL];
     int run, frame;
     if (!xcd_frame_map(P.nblur_runs, P.nframes, run, frame)) return;
     frame += P.frame0;
@@ -1016,10 +1034,10 @@ __global__ __launch_bounds__(256, 5) void k_blur_strip(ExtractParams P)
     const LevelGeom* gp = P.geom + R.level;
     BlurStrip S;
     S.gw = scalar_load(&gp->w); S.gh = scalar_load(&gp->h); S.x0 = R.x0;
-    const int gpitch = scalar_load(&gp->pitch), plane_off = scalar_load(&gp->plane_off);
-    S.spitch = (unsigned)(R.level == 0 ? P.img0_pitch : gpitch); S.dpitch = (unsigned)gpitch;
+    const int gpitch = scalar_load(&gp->pitch), plane_off = scalar_load(&gp->plane_off), blur_off = scalar_load(&gp->blur_off);
+    S.spitch = (unsigned)(R.level == 0 ? P.img0_pitch : gpitch); S.dtpr = scalar_load(&gp->blur_tpr);
     S.src = uniform_ptr(R.level == 0 ? P.img0 + (long long)frame * P.img0_frame_stride : P.pyr + (long long)frame * P.plane_frame_bytes + plane_off);
-    S.dst = uniform_ptr(P.blur + (long long)frame * P.plane_frame_bytes + plane_off);
+    S.dst = uniform_ptr(P.blur + (long long)frame * P.blur_frame_bytes + blur_off);
     const int w4 = S.gw & ~3;
     S.coff = (unsigned)min(max(S.x0 - 4 + 4 * lane, 0), S.gw - 4);      // dwords that are not entirely inside the image: see blur_strip_fix
     S.fix_left = S.x0 == 0; S.fix_right = S.x0 + 252 > w4;
@@ -1028,7 +1046,7 @@ __global__ __launch_bounds__(256, 5) void k_blur_strip(ExtractParams P)
     __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(8));                        // the band rows
     lds_barrier_spelled();
     const v4i HB1 = lds_read_b128(s_band + 4 * lane), HB2 = lds_read_b128(s_band + 256 + 4 * lane), VB = lds_read_b128(s_band + 512 + 4 * lane);
-    const int n = R.n, full = wave < 2 ? 7 : 6;
+    const int n = R.n, full = blur_stores_per_wave(blur_store_tiles_of(S.gw, S.x0), wave);
     for (int t = 0; t < n; t += 2) {                                   // (two steps per trip: the buffers swap roles with constant addresses)
         blur_strip_step(S, R.y0 + BM_ROWS * t, t + 1 < n, t ? full : 0, HB1, HB2, VB, wave, lane, s_in0, s_in1, s_out);
         if (t + 1 < n) blur_strip_step(S, R.y0 + BM_ROWS * (t + 1), t + 2 < n, full, HB1, HB2, VB, wave, lane, s_in1, s_in0, s_out);
@@ -1843,11 +1861,17 @@ __global__ __launch_bounds__(QT_T) void k_quadtree(ExtractParams P)
 // FAST / the pyramid, both precede the descriptor kernel); as two launches on one stream a frame's eight quadtree workgroups (59 us at level 0 of a
 // 1241 x 376 frame) ran behind the blur's 11 us, on two streams the event hops cost more than the blur.  The quadtree workgroups take the first
 // ids (level-major: the longest start first), the blur tiles fill the rest of the chip beside them.
+#define BQ_IN_DW (32 * BM_IN_DW)
+#define BQ_OUT_DW (BM_OUT_ROWS * BM_OUT_DW + BM_OUT_TAIL)
+#define BQ_BAND_DW (3 * 64 * 4)
+// the blur tile's static LDS beside the quadtree's dynamic block (each array rounded up to the 16-byte alignment of the next): what the host adds to
+// orbhip_quadtree_lds_bytes before it chooses this launch
+size_t orbhip_blur_quadtree_static_lds() { return (size_t)(((BQ_IN_DW * 4 + 15) & ~15) + ((BQ_OUT_DW * 4 + 15) & ~15) + ((BQ_BAND_DW * 4 + 15) & ~15)); }
 __global__ __launch_bounds__(256) void k_blur_quadtree(ExtractParams P)
 {
-    __shared__ __attribute__((aligned(16))) unsigned s_in[32 * BM_IN_DW];
-    __shared__ unsigned s_out[BM_ROWS * BM_OUT_DW];
-    __shared__ __attribute__((aligned(16))) unsigned s_band[3 * 64 * 4];
+    __shared__ __attribute__((aligned(16))) unsigned s_in[BQ_IN_DW];
+    __shared__ unsigned s_out[BQ_OUT_DW];
+    __shared__ __attribute__((aligned(16))) unsigned s_band[BQ_BAND_DW];
     HIP_DYNAMIC_SHARED(int, lds)
     const int nqt = P.nlevels * P.nframes, id = (int)blockIdx.x;
     if (id < nqt) {
@@ -1939,13 +1963,15 @@ __device__ __forceinline__ int wave_sum_dpp(int v)
 __device__ __forceinline__ int round_half_even_small(float x) { return __float_as_int(__fadd_rn(x, 12582912.0f)) - 0x4B400000; }
 
 #define DS_WAVES 4
-#define DS_KPW 4                       // key point slots per wavefront (3 and 5 measured slower: docs/ROUND_LOG.md, round 3 "describe")
+#ifndef DS_KPW
+#define DS_KPW 4                       // key point slots per wavefront (3 and 5 measured slower: docs/ROUND_LOG.md, round 3 "describe"; 3 against 4 with the tiled window: profiles/blur_tiled_window.txt)
+#endif
 #define DS_WROWS 37                    // blurred window rows: pattern reach is +-18 after rotation
-#define DS_WSTRIDE 48                  // bytes per staged window row: 37 used, starting 0..3 bytes into the row (staged from the dword boundary below cx - 18).  12 dwords, not the
-                                       // 10 that would do: the texture addresser takes an LDS-DMA pass in groups of four lanes, and a group that straddles two image rows is what
-                                       // costs - 9.1 cycles for a pass of 5.33 rows x 48 B against 20.1 for 6.4 rows x 40 B (tools/ta_ubench.hip, profiles/r03_ta_cost_*.txt)
+#define DS_WSTRIDE 64                  // bytes per staged window row = two 32-column tiles of the blurred plane: the 37 used start 0..27 bytes into the row (staged from the tile
+                                       // boundary at or below cx - 18), or 12..15 bytes when that would need a third tile column (then staged from 16 bytes into the tile)
 #define DS_PPASS 8                     // orientation patch: 32-bit load passes of 4 rows x 16 lanes
-#define DS_WPASSES 7                   // LDS-DMA passes per window: 7 x 64 dwords >= 37 rows x 12 dwords (16 slots x 1792 B = 28 KB per workgroup)
+#define DS_WPASSES 10                  // LDS-DMA passes per window, one TILE ROW each: 4 image rows x 64 bytes = 64 lanes x 4 bytes out of 2 (or 3) 128-byte lines;
+                                       // 10 tile rows hold the 37 rows from any row cy - 18 (16 slots x 2560 B = 40 KB per workgroup, four workgroups per CU)
 #define DS_WDWORDS (DS_WPASSES * 64)
 // One wavefront per DS_KPW consecutive key point slots, in three phases, so that what is per-key-point scalar work in the reference is
 // done once per lane instead of once per wave:
@@ -1962,7 +1988,7 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
     // the rBRIEF pattern (4 KB, [component][round][lane]) is fetched once per workgroup with four coalesced 32-bit loads per thread - as 16-byte
     // loads per lane it cost every wave 4 x 71 cycles of the texture addresser, more than the wave's orientation patches (tools/ta_ubench.hip) -
     // and passes through the first window buffers on its way to the lanes' registers (two barriers, before any wave leaves or stages a window):
-    // the workgroup's LDS stays at 28 KB, five workgroups per CU with room to spare
+    // the workgroup's LDS stays the windows' 40 KB
     float* s_pat = reinterpret_cast<float*>(&s_win[0][0][0]);
     static_assert(DS_KPW * DS_WDWORDS >= 16 * 64, "the pattern passes through wave 0's window buffers");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1983,6 +2009,7 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
     // then passed around with v_readlane: a chain of dependent "load, wait, readfirstlane" steps costs a memory latency each.
     const int lq = min(lane, P.nlevels - 1);
     const int g_kpoff = P.geom[lq].kp_off, g_pitch = P.geom[lq].pitch, g_poff = P.geom[lq].plane_off, g_n = P.lvl_n[frame * P.nlevels + lq];
+    const int g_boff = P.geom[lq].blur_off, g_btpr = P.geom[lq].blur_tpr;
     const float g_scale = P.geom[lq].scale, g_size = P.geom[lq].kp_size;
     const int mySlot = min(slot0 + lane, P.lvl_kp_per_frame - 1);
     const unsigned myV = P.lvl_kp[(long long)frame * P.lvl_kp_per_frame + mySlot];
@@ -2001,12 +2028,11 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
 #pragma unroll
     for (int k = 0; k < 4; k++) s_pat[256 * k + threadIdx.x] = pv[k];              // (the pattern's loads are the oldest outstanding ones: this waits for them alone)
     const unsigned ucoef = 0x03020100u + 0x04040404u * (unsigned)pd;       // u + 15 of the dword's four bytes
-    int wrow[DS_WPASSES], wcol[DS_WPASSES];                                // window DMA: pass k, lane l fills dword 64k + l = (row, dword) of the 12-dword rows
-#pragma unroll
-    for (int k = 0; k < DS_WPASSES; k++) {
-        const int pos = 64 * k + lane, row = (pos * 5462) >> 16;          // pos / 12 for pos < 448
-        wrow[k] = min(row, DS_WROWS - 1); wcol[k] = 4 * (pos - 12 * row); // the four dwords past the window re-read the start of its last row (in bounds, never used)
-    }
+    // window DMA: lane l fills dword l of a pass = (row l >> 4 of the tile row, dword l & 15 of the 64-byte span).  Its offset from the span's first tile
+    // for a span of two whole tiles, and for one that starts 16 bytes into a tile and ends 16 bytes into the next but one
+    const unsigned wcol3 = 16u + 4u * (unsigned)(lane & 15);
+    const unsigned woff2 = (unsigned)((lane & 15) >> 3) * (unsigned)ORBHIP_BT_BYTES + (unsigned)(lane >> 4) * (unsigned)ORBHIP_BT_W + 4u * (unsigned)(lane & 7);
+    const unsigned woff3 = (wcol3 >> 5) * (unsigned)ORBHIP_BT_BYTES + (unsigned)(lane >> 4) * (unsigned)ORBHIP_BT_W + (wcol3 & 31u);
 
     // ---- 0. slot -> (level, index in the level, output index), lane j for slot j; then wave-uniform copies (SGPRs) of the wave's slots.
     //      Valid slots of a wave have consecutive output indices (slots and outputs are both level-major).
@@ -2052,14 +2078,19 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
 
     // ---- 1. IC_Angle of every slot.  Every memory request of the wave is issued here, before anything is waited for: the patch loads of
     //      all slots, then the LDS-DMA of all blurred windows (one LDS buffer per slot) - a wave pays the memory latency once
+    // The blurred plane is stored as 32x4 tiles, one 128-byte line each (orbhip_blur_tile_addr): a pass is one tile row of the window and touches two lines,
+    // three when (cx - 18) & 31 > 27 - against 5 to 6 rows of 48 bytes, a line each, in a row-major plane (tools/window_gather_probe.hip).  The span's first
+    // tile goes into the scalar pointer, which moves on by one tile row per pass; the window lands row-major with a 64-byte stride.
     auto window_dma = [&](int level, unsigned v, unsigned* win) {
-        const ORBHIP_GLOBAL uint8_t* blv = uniform_ptr(P.blur + (long long)frame * P.plane_frame_bytes + RL(g_poff, level));
-        const int bpitch = RL(g_pitch, level);
-        const int cx = v & 0xfff, cy = (v >> 12) & 0xfff;
-        const unsigned base = (unsigned)((cy - 18) * bpitch + ((cx - 18) & ~3));        // rows start on a dword (planes and pitches are 64-byte aligned): 40 bytes from there still hold the 37 of the window, and an LDS-DMA pass of this shape costs the texture addresser 20 cycles instead of 25 (tools/ta_ubench.hip)
+        const int tpr = RL(g_btpr, level);
+        const int x0 = (int)(v & 0xfff) - 18, y0 = (int)((v >> 12) & 0xfff) - 18;
+        const bool three = (x0 & 31) > 27;                                 // wave-uniform
+        const unsigned tile = (unsigned)((y0 >> 2) * tpr + (x0 >> 5));     // (x0 & ~15 lies in the same tile as x0)
+        const ORBHIP_GLOBAL uint8_t* tp = uniform_ptr(P.blur + (long long)frame * P.blur_frame_bytes + RL(g_boff, level)) + tile * (unsigned)ORBHIP_BT_BYTES;
+        const unsigned woff = three ? woff3 : woff2;
+        const unsigned step = (unsigned)tpr * (unsigned)ORBHIP_BT_BYTES;
 #pragma unroll
-        for (int k = 0; k < DS_WPASSES; k++)
-            lds_dma_dword(blv + (base + __umul24((unsigned)wrow[k], (unsigned)bpitch) + (unsigned)wcol[k]), reinterpret_cast<uint8_t*>(win) + 256 * k);
+        for (int k = 0; k < DS_WPASSES; k++) { lds_dma_dword(tp + woff, reinterpret_cast<uint8_t*>(win) + 256 * k); tp += step; }
     };
     int M10 = 0, M01 = 0;
     {
@@ -2100,25 +2131,28 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
         for (int j = 0; j < DS_KPW; j++) {
             if (!ok[j]) continue;
             later--;
-            // vmcnt counts in order: at most 6 * later loads outstanding  <=>  this slot's window (and everything older) has landed
+            // vmcnt counts in order: at most DS_WPASSES * later loads outstanding  <=>  this slot's window (and everything older) has landed
             if (later >= 3) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(3 * DS_WPASSES));
             else if (later == 2) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(2 * DS_WPASSES));
             else if (later == 1) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(DS_WPASSES));
             else lds_dma_wait();
             __builtin_amdgcn_wave_barrier();
             const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a_l), j)), b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b_l), j));
-            const uint8_t* w8 = reinterpret_cast<const uint8_t*>(s_win[wave][j]) + 18 * DS_WSTRIDE + 18 + (((vv[j] & 0xfff) - 18) & 3);      // key point position inside the window (staged from the dword boundary at or below cx - 18)
+            // key point position inside the window: its first row is row (cy - 18) & 3 of the first tile row, its first column sits (cx - 18) & 31 bytes behind the tile boundary, less the 16 of the three-tile span
+            const int wx0 = (int)(vv[j] & 0xfff) - 18, wy0 = (int)((vv[j] >> 12) & 0xfff) - 18;
+            const uint8_t* w8 = reinterpret_cast<const uint8_t*>(s_win[wave][j]) + (18 + (wy0 & 3)) * DS_WSTRIDE + 18 + ((wx0 & 31) > 27 ? (wx0 & 15) : (wx0 & 31));
             const int dlane = 4 * (oi[j] - oi_first);
             // P.fp_contract (wave-uniform): 0 = x*b + y*a as two roundings (a build with -ffp-contract=off, H3), 1 = the fused forms gcc emits
             // for the reference's own flags, fma(x, b, y*a) and fma(x, a, -(y*b))
             // Both points of a test go through the rotation as one packed-f32 pair (v_pk_mul_f32 / v_pk_add_f32: every product and sum still
             // rounded on its own), and cvRound comes out of the float's own bits: x + (2^23 + 64) is an integer-valued float with ulp 1 for
-            // |x| < 64 - the same round-half-to-even as rint (64 is even) - whose low 24 bits are 64 + rint(x).  v_mad_u32_u24 takes exactly
-            // those of the row coordinate, so   (64 + iy) * 48 + bits(x') = 48 iy + ix + C   with C = 3072 + 64 + 0x4B000000:
-            // one multiply-add and one addition of a wave-uniform constant per point instead of two subtractions, a multiplication and two additions.
+            // |x| < 64 - the same round-half-to-even as rint (64 is even) - whose bits are 0x4B000000 + 64 + rint(x).  The window's rows are 64 bytes
+            // apart, so   (bits(y') << 6) + bits(x') = 64 iy + ix + C   (mod 2^32) with C = (0x4B000000 << 6) + 64 * 64 + 0x4B000000 + 64:
+            // one shift-add and one addition of a wave-uniform constant per point instead of two subtractions, a multiplication and two additions.
             typedef float f2v __attribute__((vector_size(8)));
             const f2v A2 = {a, a}, B2 = {b, b}, MG = {8388672.0f, 8388672.0f};
-            const unsigned cbias = 3072u + 64u + 0x4B000000u;
+            static_assert(DS_WSTRIDE == 64, "the BRIEF address shifts the row coordinate by 6");
+            const unsigned cbias = (0x4B000000u << 6) + 4096u + 64u + 0x4B000000u;
             auto brief = [&](auto fused) {
                 int t0[4], t1[4];
 #pragma unroll
@@ -2135,8 +2169,8 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
                         fy = X * B2 + Y * A2; fx = X * A2 - Y * B2;
                     }
                     const f2v ry = fy + MG, rx = fx + MG;
-                    const int o0 = (int)(__umul24(__float_as_uint(ry[0]), (unsigned)DS_WSTRIDE) + __float_as_uint(rx[0]) - cbias);
-                    const int o1 = (int)(__umul24(__float_as_uint(ry[1]), (unsigned)DS_WSTRIDE) + __float_as_uint(rx[1]) - cbias);
+                    const int o0 = (int)((__float_as_uint(ry[0]) << 6) + __float_as_uint(rx[0]) - cbias);
+                    const int o1 = (int)((__float_as_uint(ry[1]) << 6) + __float_as_uint(rx[1]) - cbias);
                     t0[r] = w8[o0]; t1[r] = w8[o1];
                 }
                 // all eight byte reads are out before the first comparison: with the ballots and v_writelane (an asm statement: a scheduling boundary) in the
