@@ -2,6 +2,8 @@
 per step from precomputed records): many queries competing for the same features, equal descriptors (ties), stolen matches,
 blocking and non-blocking map points, initially occupied features, every level-filter form, windows from a few pixels to the whole
 image.  Results must equal the oracle's one-query-at-a-time restatement of ORBmatcher.cc:45-129, 405-520, 1328-1470.
+A third sweep crowds the independent queries of k_best_in_window (Fuse / SearchBySim3, ORBmatcher.cc:884-948, 1188-1224) in the same way: ties decided by
+the order of the feature grid, random bounds, stereo columns, windows from one pixel to the whole table, single and batched calls.
 A few seeds on the CPU emulation of the kernels, more on the GPU; `python tests/test_fuzz_matchers.py <library> [ncases]` by hand."""
 import os
 import sys
@@ -83,6 +85,54 @@ def projection_case(rng, O, lib, frames):
     return ok
 
 
+def best_in_window_case(rng, O, lib, batch=False):
+    """search_best_in_window (Fuse / SearchBySim3's candidate loop) on synthetic key points: clustered key points under random bounds, few distinct
+    descriptors (ties), stereo columns that include 0.0, queries crowded on a few spots with windows from one pixel to the whole table"""
+    w, h = int(rng.integers(100, 700)), int(rng.integers(100, 500))
+    bounds = (0.0, 0.0, float(w), float(h))
+    if rng.random() < 0.5:
+        bounds = (float(-rng.uniform(0.5, 30)), float(-rng.uniform(0.5, 30)), float(w + rng.uniform(0.5, 30)), float(h + rng.uniform(0.5, 30)))
+    n, nq = int(rng.integers(1, 901)), int(rng.integers(1, 401))
+    spots = np.stack([rng.uniform(bounds[0] - 5, bounds[2] + 5, 12), rng.uniform(bounds[1] - 5, bounds[3] + 5, 12)], 1)
+    at = rng.integers(0, int(rng.integers(1, 13)), n)
+    k = np.zeros(n, KD)
+    k["x"], k["y"] = spots[at, 0] + rng.normal(0, rng.choice([1.0, 6.0, 40.0]), n), spots[at, 1] + rng.normal(0, rng.choice([1.0, 6.0, 40.0]), n)
+    if rng.random() < 0.3:
+        k["x"], k["y"] = np.round(k["x"]), np.round(k["y"])                       # integer coordinates: key points exactly on a radius
+    k["octave"] = rng.integers(0, 8, n)
+    base = rng.integers(0, 256, (int(rng.integers(1, 9)), 32), dtype=np.uint8)
+    d = base[rng.integers(0, len(base), n)].copy()
+    _flip(rng, d, 3)
+    ur = None
+    if rng.random() < 0.7:
+        ur = np.where(rng.random(n) < rng.random(), k["x"] - rng.uniform(0, 6, n), -1.0).astype(np.float32)
+        ur[rng.random(n) < 0.1] = 0.0
+    sf = np.float32(1.2) ** np.arange(8, dtype=np.float32)
+    inv = (1.0 / (sf * sf)).astype(np.float32)
+    q = np.zeros(nq, O.BEST_QUERY_DTYPE)
+    c = rng.integers(0, int(rng.integers(1, 13)), nq)
+    q["x"], q["y"] = spots[c, 0] + rng.normal(0, 2, nq), spots[c, 1] + rng.normal(0, 2, nq)
+    if rng.random() < 0.3:
+        q["x"], q["y"] = np.round(q["x"]), np.round(q["y"])
+    q["radius"] = rng.choice([1.0, 3.0, 8.0, 20.0, 60.0, 600.0], nq)
+    q["ur"] = q["x"] - rng.uniform(0, 6, nq)
+    q["level"] = rng.integers(0, 8, nq)
+    qd = base[rng.integers(0, len(base), nq)].copy()
+    _flip(rng, qd, 3)
+    ok = True
+    for chi2 in (False, True):
+        with O.image_bounds_set(bounds):
+            bi_o, bd_o = O.search_best_in_window(k, d, w, h, inv, q, qd, chi2, u_right=ur)
+        if batch:                                                                 # as the middle one of three slots, its neighbours other frames under other bounds
+            other = dict(kps=k[:n // 2], desc=d[:n // 2], u_right=None, bounds=(0.0, 0.0, 800.0, 600.0), inv_level_sigma2=inv, queries=q[:nq // 3], qdesc=qd[:nq // 3])
+            bi_g, bd_g = orb_slam2_amd.search_best_in_window_batch([other, dict(kps=k, desc=d, u_right=ur, bounds=bounds, inv_level_sigma2=inv, queries=q, qdesc=qd), other],
+                                                                   chi2, library=lib)[1]
+        else:
+            bi_g, bd_g = orb_slam2_amd.search_best_in_window(k, d, w, h, inv, q, qd, chi2, u_right=ur, bounds=bounds, library=lib)
+        ok &= np.array_equal(bi_g, bi_o) and np.array_equal(bd_g, bd_o)
+    return ok
+
+
 @pytest.fixture(scope="module")
 def frames(oracle):
     w, h, n = 480, 360, 700
@@ -105,6 +155,11 @@ def test_projection_conflicts(backend, oracle, frames):
         assert projection_case(np.random.default_rng(1000 + t), oracle, backend, frames), f"case {t}"
 
 
+def test_best_in_window_conflicts(backend, oracle):
+    for t in range(_ncases(backend, 8, 60)):
+        assert best_in_window_case(np.random.default_rng(4000 + t), oracle, backend, batch=t % 4 == 3), f"case {t}"
+
+
 if __name__ == "__main__":
     from oracle import orb_oracle as O
     lib = sys.argv[1]
@@ -117,5 +172,6 @@ if __name__ == "__main__":
     for t in range(ncases):
         bad += not initialization_case(np.random.default_rng(7000 + t), O, lib)
         bad += not projection_case(np.random.default_rng(1000 + t), O, lib, fr)
-    print(f"{2 * ncases} cases, {bad} mismatches")
+        bad += not best_in_window_case(np.random.default_rng(4000 + t), O, lib, batch=t % 4 == 3)
+    print(f"{3 * ncases} cases, {bad} mismatches")
     sys.exit(1 if bad else 0)
