@@ -263,6 +263,37 @@ orbhip_status orbhip_pose_optimization_frame(orbhip_ctx* ctx, int frame, const o
                                              const int32_t* idx /* m */, const float* xyz /* 3 m */, int m,
                                              float* Tcw_out /* 16 */, uint8_t* outlier /* m */, int* n_inliers);
 
+/* Sim3Solver::iterate (Sim3Solver.cc:140-207): loop closing's RANSAC over n 3-D to 3-D correspondences between two key frames.  The caller draws
+   the minimal sets (`triples`: 3 indices per hypothesis, each in 0..n-1 and distinct within a triple - the solver's swap-remove draw guarantees both);
+   the device solves Horn's closed form for every hypothesis (ComputeSim3), counts its inliers against every correspondence (CheckInliers) and replays
+   the loop over the counts in hypothesis order, starting from best_inliers_in (mnBestInliers): a count >= the running best is a new best (a later tie
+   wins), a new best with count > min_inliers returns there and later hypotheses are not consumed.  The caller passes n_hyp = min(nIterations,
+   mRansacMaxIts - mnIterations).  The arithmetic is DESIGN.md H17: float where the reference holds a CV_32F Mat or a float member, double between.
+   gemm_mode is H11's (0 or 1); mode 2 cannot be served - every product is per hypothesis on the device - and is ORBHIP_ERR_UNSUPPORTED.
+   sigma2_1/2 are mvLevelSigma2 of the two key points' octaves (finite, >= 0): the thresholds are (float)(size_t)(9.210 * sigma2), 9 at level 0.
+   Outputs: n_consumed hypotheses; returned = the hypothesis that returned or -1; best = the last new best or -1; best_inliers_out = mnBestInliers
+   after the call; with best >= 0 also T12 (mBestT12, row-major 4 x 4), R12, t12, s12 and inliers (mvbBestInliers, n bytes) - with best = -1 they are
+   not written.  The optional per-hypothesis outputs (NULL: skipped) hold EVERY hypothesis of the call, consumed or not: hyp_R 9 n_hyp, hyp_t 3 n_hyp,
+   hyp_s and hyp_count n_hyp, hyp_mask n_hyp x ((n + 63) / 64) words, bit i & 63 of word i / 64 = correspondence i.
+   With n < 3 or n_hyp == 0 a problem is answered at once: n_consumed = 0, returned = best = -1, nothing else written.  n_hyp above 4096, a bad index,
+   a NULL corr / triples / inliers: ORBHIP_ERR_INVALID, nothing computed.  Two launches, one upload and one download per call whatever the number of
+   problems; results repeat bit for bit and do not depend on a problem's place in a batch.  Re-entrant like the pose-optimisation entries. */
+typedef struct { float X1[3] /* mvX3Dc1 */, X2[3] /* mvX3Dc2 */, sigma2_1, sigma2_2; } orbhip_sim3_corr;
+typedef struct {
+    float K1[4], K2[4];         /* fx, fy, cx, cy of mK1, mK2 */
+    const orbhip_sim3_corr* corr; int32_t n;
+    int32_t fix_scale, gemm_mode;
+    const int32_t* triples; int32_t n_hyp;
+    int32_t min_inliers, best_inliers_in;
+    int32_t n_consumed, returned, best, best_inliers_out;
+    float T12[16], R12[9], t12[3], s12;
+    uint8_t* inliers;           /* n bytes */
+    float* hyp_R; float* hyp_t; float* hyp_s; int32_t* hyp_count; uint64_t* hyp_mask;
+} orbhip_sim3_problem;
+orbhip_status orbhip_sim3_iterate(int device, orbhip_sim3_problem* problem);
+/* one round of LoopClosing::ComputeSim3's candidate loop: independent solvers of any mix of sizes */
+orbhip_status orbhip_sim3_iterate_batch(int device, int nproblems, orbhip_sim3_problem* problems);
+
 /* ORBmatcher(nnratio, check_ori).SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, window)
    (ORBmatcher.h:69, ORBmatcher.cc:405-520) on host buffers.  The Frame members it reads are passed flat:
    mvKeysUn / mDescriptors of both frames and the image bounds (mnMinX = mnMinY = 0, mnMaxX = im_w,

@@ -20,7 +20,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
 
 # every symbol include/orbhip.h declares (tests check the library exports all of them)
 SYMBOLS = [
-    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
+    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_sim3_iterate", "orbhip_sim3_iterate_batch", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
     "orbhip_get_scale_tables", "orbhip_level_size", "orbhip_extract", "orbhip_extract_batch", "orbhip_pyramid_level",
     "orbhip_extract_device", "orbhip_sync", "orbhip_fetch", "orbhip_fetch_matches", "orbhip_descriptor_distance",
     "orbhip_hamming_nn", "orbhip_hamming_nn_device", "orbhip_nn_expanded_size", "orbhip_nn_expand_device", "orbhip_hamming_nn_device_expanded", "orbhip_search_for_initialization", "orbhip_profile_enable",
@@ -192,6 +192,8 @@ def lib(path=None):
     L.orbhip_pose_optimization.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]
     L.orbhip_pose_optimization_batch.argtypes = [C.c_int, C.c_int, vp]
     L.orbhip_pose_optimization_frame.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.orbhip_sim3_iterate.argtypes = [C.c_int, vp]
+    L.orbhip_sim3_iterate_batch.argtypes = [C.c_int, C.c_int, vp]
     L.orbhip_hamming_nn_device.argtypes = [vp, vp, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.orbhip_nn_expanded_size.argtypes = [C.c_int64]; L.orbhip_nn_expanded_size.restype = C.c_size_t
     L.orbhip_nn_expand_device.argtypes = [vp, vp, C.c_int64, vp]
@@ -997,6 +999,76 @@ def pose_optimization_batch(problems, device=None, library=None):
     L = lib(library)
     _check(L.orbhip_pose_optimization_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_pose_optimization_batch", L)
     return [(np.array(arr[k].Tcw_out[:], np.float32).reshape(4, 4), keep[k][1].astype(bool), int(arr[k].n_inliers)) for k in range(n)]
+
+
+SIM3_CORR_DTYPE = np.dtype([("X1", "<f4", 3), ("X2", "<f4", 3), ("sigma2_1", "<f4"), ("sigma2_2", "<f4")])                                       # orbhip_sim3_corr
+
+
+class _Sim3Problem(C.Structure):                                                # orbhip_sim3_problem
+    _fields_ = [("K1", C.c_float * 4), ("K2", C.c_float * 4), ("corr", C.c_void_p), ("n", C.c_int32), ("fix_scale", C.c_int32), ("gemm_mode", C.c_int32),
+                ("triples", C.c_void_p), ("n_hyp", C.c_int32), ("min_inliers", C.c_int32), ("best_inliers_in", C.c_int32),
+                ("n_consumed", C.c_int32), ("returned", C.c_int32), ("best", C.c_int32), ("best_inliers_out", C.c_int32),
+                ("T12", C.c_float * 16), ("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float),
+                ("inliers", C.c_void_p), ("hyp_R", C.c_void_p), ("hyp_t", C.c_void_p), ("hyp_s", C.c_void_p), ("hyp_count", C.c_void_p), ("hyp_mask", C.c_void_p)]
+
+
+def _sim3_corr(corr):
+    corr = np.asarray(corr)
+    return np.ascontiguousarray(corr if corr.dtype == SIM3_CORR_DTYPE else np.ascontiguousarray(corr, np.float32).reshape(-1, 8).view(SIM3_CORR_DTYPE).reshape(-1))
+
+
+def _sim3_fill(rec, problem, per_hypothesis):
+    """one orbhip_sim3_problem from a dict; returns the arrays the record points to"""
+    corr = _sim3_corr(problem["corr"])
+    tri = np.ascontiguousarray(problem["triples"], np.int32).reshape(-1, 3)
+    n, nh, words = len(corr), len(tri), (len(corr) + 63) // 64
+    rec.K1[:] = [float(v) for v in np.ascontiguousarray(problem["K1"], np.float32).reshape(4)]
+    rec.K2[:] = [float(v) for v in np.ascontiguousarray(problem["K2"], np.float32).reshape(4)]
+    rec.n, rec.n_hyp = n, nh
+    rec.fix_scale, rec.gemm_mode = int(bool(problem.get("fix_scale", True))), int(problem.get("gemm_mode", 0))
+    rec.min_inliers, rec.best_inliers_in = int(problem.get("min_inliers", 6)), int(problem.get("best_inliers_in", 0))
+    keep = {"corr": corr, "triples": tri, "inliers": np.zeros(n, np.uint8)}
+    if per_hypothesis:
+        keep.update(hyp_R=np.zeros((nh, 3, 3), np.float32), hyp_t=np.zeros((nh, 3), np.float32), hyp_s=np.zeros(nh, np.float32),
+                    hyp_count=np.zeros(nh, np.int32), hyp_mask=np.zeros((nh, words), np.uint64))
+    for k, a in keep.items():
+        setattr(rec, k, a.ctypes.data if a.size else None)
+    return keep
+
+
+def _sim3_result(rec, keep):
+    out = {"n_consumed": int(rec.n_consumed), "returned": int(rec.returned), "best": int(rec.best), "best_inliers_out": int(rec.best_inliers_out)}
+    if rec.best >= 0:
+        out.update(T12=np.array(rec.T12[:], np.float32).reshape(4, 4), R12=np.array(rec.R12[:], np.float32).reshape(3, 3), t12=np.array(rec.t12[:], np.float32),
+                   s12=np.float32(rec.s12), inliers=keep["inliers"].astype(bool))
+    else:
+        out.update(T12=None, R12=None, t12=None, s12=None, inliers=None)
+    for k in ("hyp_R", "hyp_t", "hyp_s", "hyp_count", "hyp_mask"):
+        if k in keep:
+            out[k] = keep[k]
+    return out
+
+
+def sim3_iterate(K1, K2, corr, triples, fix_scale=True, gemm_mode=0, min_inliers=6, best_inliers_in=0, per_hypothesis=False, device=None, library=None):
+    """One call of Sim3Solver::iterate on the device (orbhip_sim3_iterate): K1, K2 = (fx, fy, cx, cy); corr an array of SIM3_CORR_DTYPE (or n x 8
+    float32: X1c, X2c, sigma2_1, sigma2_2); triples n_hyp x 3 drawn indices.  Returns a dict: n_consumed, returned, best, best_inliers_out, and - None
+    where best is -1 - T12, R12, t12, s12, inliers; with per_hypothesis also hyp_R, hyp_t, hyp_s, hyp_count, hyp_mask of every hypothesis."""
+    return sim3_iterate_batch([dict(K1=K1, K2=K2, corr=corr, triples=triples, fix_scale=fix_scale, gemm_mode=gemm_mode, min_inliers=min_inliers,
+                                    best_inliers_in=best_inliers_in)], per_hypothesis=per_hypothesis, device=device, library=library, _single=True)[0]
+
+
+def sim3_iterate_batch(problems, per_hypothesis=False, device=None, library=None, _single=False):
+    """Independent solvers in one device call (orbhip_sim3_iterate_batch): problems is a sequence of dicts with the keyword names of sim3_iterate.
+    Returns a list of result dicts."""
+    n = len(problems)
+    arr = (_Sim3Problem * max(n, 1))()
+    keep = [_sim3_fill(arr[k], q, per_hypothesis) for k, q in enumerate(problems)]
+    L = lib(library)
+    if _single:
+        _check(L.orbhip_sim3_iterate(0 if device is None else device, C.cast(arr, C.c_void_p)), "orbhip_sim3_iterate", L)
+    else:
+        _check(L.orbhip_sim3_iterate_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_sim3_iterate_batch", L)
+    return [_sim3_result(arr[k], keep[k]) for k in range(n)]
 
 
 def nn_expanded_size(ndb, library=None):
