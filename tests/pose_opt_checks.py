@@ -96,6 +96,33 @@ def check_batch_slots(library):
     assert orb_slam2_amd.pose_optimization_batch([], library=library) == []
 
 
+# (the first live problem is the smallest: a launch sized by it, and not by the largest, would leave n2048 without its LDS)
+BATCH_EDGES = ["zero_residual", "n2048_mixed_30", "turn_123_m130", None, "n2049_mixed_30", "all_outliers_300", "turn_y_pi_exact", "behind_camera"]
+
+
+def check_batch_edges(library):
+    """the size and degenerate cases side by side in one batch.  The launch takes its LDS size from the largest problem: n2049 (not staged) next to n2048
+    (staged, and so in need of all 2048 x 28 bytes) is a batch whose largest problem does not stage.  Every slot equals its own single call bit for bit and
+    the model's flags and count; the problem with 2 observations is untouched."""
+    short = case("n10_mono_0")
+    probs = [case(n)[:3] if n else (short[0], short[1], short[2][:2]) for n in BATCH_EDGES]
+    out = orb_slam2_amd.pose_optimization_batch(probs, library=library)
+    assert len(out) == len(BATCH_EDGES)
+    for k, n in enumerate(BATCH_EDGES):
+        if n is None:
+            assert out[k][2] == 0 and not out[k][1].any() and len(out[k][1]) == 2 and out[k][0].tobytes() == short[1].tobytes()
+            continue
+        one = orb_slam2_amd.pose_optimization(*case(n)[:3], library=library)
+        assert out[k][0].tobytes() == one[0].tobytes() and np.array_equal(out[k][1], one[1]) and out[k][2] == one[2], (k, n)
+        assert np.array_equal(out[k][1], case(n)[4]) and out[k][2] == case(n)[5], (k, n)
+        ok, over = pose_close(out[k][0], case(n)[3], case(n)[6])
+        assert ok, (k, n, over)
+    # what the degenerate slots are there for: nothing left, nothing flagged, and the two poses that may not move
+    a, z = out[BATCH_EDGES.index("all_outliers_300")], out[BATCH_EDGES.index("zero_residual")]
+    assert a[2] == 0 and a[1].all() and a[0].tobytes() == M.to_cvmat(M.to_se3quat(case("all_outliers_300")[1])).tobytes()
+    assert z[2] == 40 and not z[1].any() and z[0].tobytes() == case("zero_residual")[1].tobytes()
+
+
 def check_short_untouched(library):
     """n < 3 leaves the pose buffer and the flags untouched"""
     L = orb_slam2_amd.lib(library)

@@ -1,6 +1,6 @@
 """orbhip_pose_optimization (orb_slam2_amd/csrc/orbhip_pose_opt.hip) under CPU emulation against tests/pose_opt_model.py: every case of
 tests/pose_opt_cases.py (sizes around the wave, the workgroup and the LDS staging limit; monocular, stereo and mixed edges; with and without gross
-outliers), bit-for-bit repeatability, batch slots, the frame form, the short cases, the C++ drop-in (also under AddressSanitizer and UBSan as a stand-alone
+outliers; initial rotations past 120 degrees; every edge an outlier, zero residuals, points behind the camera, a float-product pose), bit-for-bit repeatability, batch slots, the frame form, the short cases, the C++ drop-in (also under AddressSanitizer and UBSan as a stand-alone
 program).  The checks themselves are in tests/pose_opt_checks.py, shared with the device run (tests/test_pose_opt_gpu.py)."""
 import numpy as np
 import pytest
@@ -22,6 +22,10 @@ def test_repeated_call_gives_the_same_bits(emu_lib):
 
 def test_batch_slots_give_the_same_bits(emu_lib):
     K.check_batch_slots(emu_lib)
+
+
+def test_batch_of_size_and_degenerate_cases(emu_lib):
+    K.check_batch_edges(emu_lib)
 
 
 def test_frame_form_equals_host_array_form(emu_lib):

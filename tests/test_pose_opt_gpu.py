@@ -21,6 +21,10 @@ def test_batch_slots_give_the_same_bits(gpu_lib):
     K.check_batch_slots(gpu_lib)
 
 
+def test_batch_of_size_and_degenerate_cases(gpu_lib):
+    K.check_batch_edges(gpu_lib)
+
+
 def test_frame_form_equals_host_array_form(gpu_lib):
     K.check_frame_form(gpu_lib)
 

@@ -111,6 +111,81 @@ def test_round_without_a_level_0_edge_returns_at_once():
     assert T.tobytes() == M.to_cvmat(init).tobytes() and len(tr["flags"]) == 4 and ninl == 12 - flags.sum()
 
 
+def _turns():
+    """(label, unit axis, angle in rad, double rotation matrix): the turned cases' axes and angles, the two exact float blocks among them as they are, and
+    100 seeded random axes with angles in (120, 180] degrees.  The matrices come from Rodrigues' formula (Cs.axis_angle), which shares nothing with the model."""
+    out = []
+    for a, deg in Cs.TURN_ANGLES:
+        axis = np.asarray(Cs.TURN_AXES[a]) / np.linalg.norm(Cs.TURN_AXES[a])
+        out.append((f"{a} {deg:+.0f}", axis, np.radians(deg), Cs.axis_angle(axis, deg)))
+        if deg == 180.0:
+            out.append((f"{a} pi exact", axis, np.pi, Cs.TURN_PI[a]))
+    out.append(("111 120 exact", np.ones(3) / np.sqrt(3.0), 2.0 * np.pi / 3.0, Cs.TURN_CYCLIC))
+    # an axis almost along one coordinate with 1e-5 of another: two diagonal entries differ by 1e-10, and taking any but the largest makes the radicand
+    # 4 q_i^2 = 4e-10 sin^2(a/2) out of numbers of size 1 - the choice of i is what keeps the precision, and only such a rotation shows a wrong choice
+    for d in range(3):
+        for s in range(3):
+            if s != d:
+                axis = np.zeros(3); axis[d] = 1.0; axis[s] = 1e-5; axis /= np.linalg.norm(axis)
+                out += [(f"axis {d} + 1e-5 axis {s}, {deg:+.0f}", axis, np.radians(deg), Cs.axis_angle(axis, deg)) for deg in (130.0, -130.0, 175.0, -175.0)]
+    rng = np.random.default_rng(120)
+    for k in range(100):
+        axis = rng.normal(0, 1, 3); axis /= np.linalg.norm(axis)
+        deg = 180.0 - rng.uniform(0.0, 60.0) * (k > 0)                          # (120, 180], the first one 180 itself
+        out.append((f"random {k}", axis, np.radians(deg), Cs.axis_angle(axis, deg)))
+    return out
+
+
+def test_quaternion_of_a_rotation_past_120_degrees():
+    """quat_of_matrix's trace <= 0 half and normalize_rotation's flip - what every turned case of the kernel tests is compared with - against the closed
+    form: a rotation by a about the unit axis n has q = (n sin(a/2), cos(a/2)), up to the sign that makes w >= 0; and rotation_matrix gives R back.
+
+    Bound 1e-14 per entry, for both.  R's entries are sums of three products of numbers below 1, each rounded: a few 1e-16 absolute.  In the trace <= 0
+    half the radicand is 1 + m_ii - m_jj - m_kk = 4 q_i^2 with q_i the largest of x, y, z; trace <= 0 means w^2 <= 1/4, so x^2 + y^2 + z^2 >= 3/4 and
+    q_i >= 0.5: the radicand is >= 1 and the few 1e-16 it carries stay a few 1e-16 through the square root and the division by 2 q_i >= 1 that gives the
+    other three entries (sums and differences of two entries of R: 4e-16 at most each).  The normalisation divides by 1 + O(1e-16).  rotation_matrix
+    multiplies pairs of entries and doubles: about ten roundings of numbers below 2.  Forty times 2.2e-16 covers it; a wrong sign or index changes an
+    entry by the size of 2 w q_i >= 0.4 at 130 degrees, thirteen orders above the bound.  At |w| below the bound itself (the half turns) q and -q are the
+    same statement, so the overall sign is left open there, and only there; w >= 0 is asserted always."""
+    bound = 1e-14
+    worst_q = worst_r = 0.0
+    took = set()
+    for label, axis, a, R in _turns():
+        want = np.concatenate([axis * np.sin(a / 2.0), [np.cos(a / 2.0)]])
+        if want[3] < 0:
+            want = -want
+        raw = M.quat_of_matrix(R)
+        q = M.normalize_rotation(raw)
+        assert q[3] >= 0, label
+        dq = np.abs(q - want).max()
+        if abs(want[3]) < bound:
+            dq = min(dq, np.abs(q + want).max())
+        dr = np.abs(M.rotation_matrix(q) - R).max()
+        worst_q, worst_r = max(worst_q, dq), max(worst_r, dr)
+        assert dq <= bound and dr <= bound, (label, dq, dr, q, want)
+        if R[0, 0] + R[1, 1] + R[2, 2] <= 0.0:
+            took.add((int(np.argmax(np.diag(R))), bool(raw[3] < 0)))
+    print(f"{len(_turns())} rotations: largest |q - closed form| {worst_q:.3e}, largest |rotation_matrix(q) - R| {worst_r:.3e}, bound {bound:.1e}; (i, w < 0) taken {sorted(took)}")
+    assert took == {(i, s) for i in range(3) for s in (False, True)}            # every largest diagonal entry, with w of either sign before the flip
+
+
+def test_turned_and_degenerate_cases_show_what_they_are_for():
+    """the preconditions tests/golden/make_golden_pose_opt_spread.py asserted when it kept the seeds, once more on the kept seeds: the turned cases take
+    every i of the trace <= 0 half with w of either sign and the two exact traces, the control does not; the degenerate cases are degenerate"""
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden_pose_opt_spread.py")
+    spec = importlib.util.spec_from_file_location("make_golden_pose_opt_spread", path)
+    G = importlib.util.module_from_spec(spec); spec.loader.exec_module(G)
+    g = np.load(os.path.join(os.path.dirname(path), "pose_opt_spread.npz"))
+    b = {n: G.quaternion_branch(Cs.case(n, int(g[n + "/seed"]))[1]) for n in Cs.TURNED}
+    assert b.pop("turn_y_p110")[1] is None
+    assert {(v[1], v[2]) for v in b.values()} >= {(i, s) for i in range(3) for s in (False, True)}
+    assert b["turn_111_120_exact"][0] == 0.0 and all(b[f"turn_{a}_pi_exact"][0] == -1.0 for a in "xyz") and all(v[0] <= 0.0 for v in b.values())
+    for n in ("all_outliers_12", "all_outliers_300", "zero_residual", "behind_camera", "float_product_pose"):
+        assert G.preconditions(n, int(g[n + "/seed"])) is None, n
+
+
 def camera_centre_problem():
     """n65_mixed_30 of the case set with R = I in the initial pose and point 5 exactly at the initial camera centre (with R = I the centre -t is a float
     vector, so R X + t is exactly 0): that edge's chi2 is non-finite from the first evaluation on"""
