@@ -294,6 +294,41 @@ orbhip_status orbhip_sim3_iterate(int device, orbhip_sim3_problem* problem);
 /* one round of LoopClosing::ComputeSim3's candidate loop: independent solvers of any mix of sizes */
 orbhip_status orbhip_sim3_iterate_batch(int device, int nproblems, orbhip_sim3_problem* problems);
 
+/* PnPsolver::iterate (PnPsolver.cc:165-258): relocalisation's RANSAC over n 3-D to 2-D correspondences of one frame and one candidate key frame.
+   The caller draws the minimal sets (`quads`: 4 indices per hypothesis, each in 0..n-1 and distinct within a quadruple, as the solver's swap-remove
+   draw gives them); the device solves EPnP for every hypothesis (compute_pose), counts its inliers (CheckInliers), replays the loop over the counts in
+   hypothesis order, starting from best_inliers_in / best_mask_in (mnBestInliers, mvbBestInliers), refines every distinct best mask the loop can meet
+   (Refine: EPnP over the mask's set bits, CheckInliers over all n) and finds the first hypothesis whose then-current mask refines with more than
+   min_inliers.  A hypothesis with count >= min_inliers refines the standing best mask; one with count > the running best (strict) replaces it first.
+   The caller passes n_hyp = max(nIterations, mRansacMaxIts - mnIterations) (the loop's OR).  The arithmetic is DESIGN.md H18, restated in
+   tests/pnp_model.py: double throughout EPnP, the mixed float / double of CheckInliers; max_error is mvMaxError (sigma2 * th2, in float).
+   Outputs: n_consumed hypotheses; returned = the hypothesis whose refine succeeded or -1; best = the last strict new best among the consumed or -1;
+   best_inliers_out = mnBestInliers after the call; with best >= 0 best_Tcw (mBestTcw, row-major 4 x 4) and best_mask (n bytes), with best = -1
+   they are not written (the carried-in ones stand); with returned >= 0 refined_Tcw, refined_inliers and refined_mask (n bytes).
+   Optional outputs (NULL: skipped): every hypothesis of the call, consumed or not - hyp_R 9 n_hyp and hyp_t 3 n_hyp doubles, hyp_count n_hyp,
+   hyp_mask n_hyp x ((n + 63) / 64) words, bit i & 63 of word i / 64 = correspondence i - and every refined candidate in the loop's order, at most
+   ref_cap of them: ref_hyp (the hypothesis whose mask it is, -1 for the carried-in mask), ref_R, ref_t, ref_count, ref_mask; n_ref is their number.
+   With n < 4, n < min_inliers or n_hyp == 0 a problem is answered at once: n_consumed = 0, returned = best = -1, nothing else written.  n_hyp above
+   4096, a bad or repeated index, a negative min_inliers, a NULL corr / quads / best_mask / refined_mask, best_inliers_in > 0 without best_mask_in:
+   ORBHIP_ERR_INVALID, nothing computed.  Four launches, one upload and one download per call whatever the number of problems; results repeat bit for
+   bit and do not depend on a problem's place in a batch.  Re-entrant like the Sim3 entries. */
+typedef struct { float Xw[3] /* mvP3Dw */, u, v /* mvP2D */, max_error /* mvMaxError */; } orbhip_pnp_corr;
+typedef struct {
+    float K[4];                 /* fx, fy, cx, cy */
+    const orbhip_pnp_corr* corr; int32_t n;
+    const int32_t* quads; int32_t n_hyp;
+    int32_t min_inliers, best_inliers_in;
+    const uint8_t* best_mask_in; /* n bytes; required when best_inliers_in > 0 */
+    int32_t n_consumed, returned, best, best_inliers_out, refined_inliers, n_ref;
+    float best_Tcw[16], refined_Tcw[16];
+    uint8_t* best_mask; uint8_t* refined_mask;      /* n bytes each */
+    double* hyp_R; double* hyp_t; int32_t* hyp_count; uint64_t* hyp_mask;
+    int32_t ref_cap; int32_t* ref_hyp; double* ref_R; double* ref_t; int32_t* ref_count; uint64_t* ref_mask;
+} orbhip_pnp_problem;
+orbhip_status orbhip_pnp_iterate(int device, orbhip_pnp_problem* problem);
+/* one round of Tracking::Relocalization's candidate loop: independent solvers of any mix of sizes */
+orbhip_status orbhip_pnp_iterate_batch(int device, int nproblems, orbhip_pnp_problem* problems);
+
 /* ORBmatcher(nnratio, check_ori).SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, window)
    (ORBmatcher.h:69, ORBmatcher.cc:405-520) on host buffers.  The Frame members it reads are passed flat:
    mvKeysUn / mDescriptors of both frames and the image bounds (mnMinX = mnMinY = 0, mnMaxX = im_w,

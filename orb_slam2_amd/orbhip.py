@@ -20,7 +20,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
 
 # every symbol include/orbhip.h declares (tests check the library exports all of them)
 SYMBOLS = [
-    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_sim3_iterate", "orbhip_sim3_iterate_batch", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
+    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_sim3_iterate", "orbhip_sim3_iterate_batch", "orbhip_pnp_iterate", "orbhip_pnp_iterate_batch", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
     "orbhip_get_scale_tables", "orbhip_level_size", "orbhip_extract", "orbhip_extract_batch", "orbhip_pyramid_level",
     "orbhip_extract_device", "orbhip_sync", "orbhip_fetch", "orbhip_fetch_matches", "orbhip_descriptor_distance",
     "orbhip_hamming_nn", "orbhip_hamming_nn_device", "orbhip_nn_expanded_size", "orbhip_nn_expand_device", "orbhip_hamming_nn_device_expanded", "orbhip_search_for_initialization", "orbhip_profile_enable",
@@ -194,6 +194,8 @@ def lib(path=None):
     L.orbhip_pose_optimization_frame.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.orbhip_sim3_iterate.argtypes = [C.c_int, vp]
     L.orbhip_sim3_iterate_batch.argtypes = [C.c_int, C.c_int, vp]
+    L.orbhip_pnp_iterate.argtypes = [C.c_int, vp]
+    L.orbhip_pnp_iterate_batch.argtypes = [C.c_int, C.c_int, vp]
     L.orbhip_hamming_nn_device.argtypes = [vp, vp, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.orbhip_nn_expanded_size.argtypes = [C.c_int64]; L.orbhip_nn_expanded_size.restype = C.c_size_t
     L.orbhip_nn_expand_device.argtypes = [vp, vp, C.c_int64, vp]
@@ -1069,6 +1071,84 @@ def sim3_iterate_batch(problems, per_hypothesis=False, device=None, library=None
     else:
         _check(L.orbhip_sim3_iterate_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_sim3_iterate_batch", L)
     return [_sim3_result(arr[k], keep[k]) for k in range(n)]
+
+
+PNP_CORR_DTYPE = np.dtype([("Xw", "<f4", 3), ("u", "<f4"), ("v", "<f4"), ("max_error", "<f4")])                                                  # orbhip_pnp_corr
+
+
+class _PnpProblem(C.Structure):                                                 # orbhip_pnp_problem
+    _fields_ = [("K", C.c_float * 4), ("corr", C.c_void_p), ("n", C.c_int32), ("quads", C.c_void_p), ("n_hyp", C.c_int32),
+                ("min_inliers", C.c_int32), ("best_inliers_in", C.c_int32), ("best_mask_in", C.c_void_p),
+                ("n_consumed", C.c_int32), ("returned", C.c_int32), ("best", C.c_int32), ("best_inliers_out", C.c_int32), ("refined_inliers", C.c_int32), ("n_ref", C.c_int32),
+                ("best_Tcw", C.c_float * 16), ("refined_Tcw", C.c_float * 16), ("best_mask", C.c_void_p), ("refined_mask", C.c_void_p),
+                ("hyp_R", C.c_void_p), ("hyp_t", C.c_void_p), ("hyp_count", C.c_void_p), ("hyp_mask", C.c_void_p),
+                ("ref_cap", C.c_int32), ("ref_hyp", C.c_void_p), ("ref_R", C.c_void_p), ("ref_t", C.c_void_p), ("ref_count", C.c_void_p), ("ref_mask", C.c_void_p)]
+
+
+def _pnp_corr(corr):
+    corr = np.asarray(corr)
+    return np.ascontiguousarray(corr if corr.dtype == PNP_CORR_DTYPE else np.ascontiguousarray(corr, np.float32).reshape(-1, 6).view(PNP_CORR_DTYPE).reshape(-1))
+
+
+def _pnp_fill(rec, problem, per_hypothesis):
+    """one orbhip_pnp_problem from a dict; returns the arrays the record points to"""
+    corr = _pnp_corr(problem["corr"])
+    quads = np.ascontiguousarray(problem["quads"], np.int32).reshape(-1, 4)
+    n, nh, words = len(corr), len(quads), (len(corr) + 63) // 64
+    rec.K[:] = [float(v) for v in np.ascontiguousarray(problem["K"], np.float32).reshape(4)]
+    rec.n, rec.n_hyp = n, nh
+    rec.min_inliers, rec.best_inliers_in = int(problem.get("min_inliers", 8)), int(problem.get("best_in", 0))
+    keep = {"corr": corr, "quads": quads, "best_mask": np.zeros(n, np.uint8), "refined_mask": np.zeros(n, np.uint8)}
+    if problem.get("best_mask_in") is not None:
+        keep["best_mask_in"] = np.ascontiguousarray(np.asarray(problem["best_mask_in"]).astype(bool), np.uint8).reshape(n)
+    if per_hypothesis:
+        cap = min(nh, n + 1) + 1
+        rec.ref_cap = cap
+        keep.update(hyp_R=np.zeros((nh, 3, 3), np.float64), hyp_t=np.zeros((nh, 3), np.float64), hyp_count=np.zeros(nh, np.int32), hyp_mask=np.zeros((nh, words), np.uint64),
+                    ref_hyp=np.zeros(cap, np.int32), ref_R=np.zeros((cap, 3, 3), np.float64), ref_t=np.zeros((cap, 3), np.float64), ref_count=np.zeros(cap, np.int32),
+                    ref_mask=np.zeros((cap, words), np.uint64))
+    for k, a in keep.items():
+        setattr(rec, k, a.ctypes.data if a.size else None)
+    return keep
+
+
+def _pnp_result(rec, keep):
+    out = {k: int(getattr(rec, k)) for k in ("n_consumed", "returned", "best", "best_inliers_out")}
+    out.update(best_Tcw=None, best_mask=None, refined_Tcw=None, refined_inliers=None, refined_mask=None)
+    if rec.best >= 0:
+        out.update(best_Tcw=np.array(rec.best_Tcw[:], np.float32).reshape(4, 4), best_mask=keep["best_mask"].astype(bool))
+    if rec.returned >= 0:
+        out.update(refined_Tcw=np.array(rec.refined_Tcw[:], np.float32).reshape(4, 4), refined_inliers=int(rec.refined_inliers), refined_mask=keep["refined_mask"].astype(bool))
+    if "hyp_R" in keep:
+        for k in ("hyp_R", "hyp_t", "hyp_count", "hyp_mask"):
+            out[k] = keep[k]
+        for k in ("ref_hyp", "ref_R", "ref_t", "ref_count", "ref_mask"):
+            out[k] = keep[k][:int(rec.n_ref)]
+    return out
+
+
+def pnp_iterate(K, corr, quads, min_inliers, best_in=0, best_mask_in=None, per_hypothesis=False, library=None, device=None):
+    """One call of PnPsolver::iterate on the device (orbhip_pnp_iterate): K = (fx, fy, cx, cy); corr an array of PNP_CORR_DTYPE (or n x 6 float32:
+    Xw, u, v, max_error); quads n_hyp x 4 drawn indices; best_in / best_mask_in the solver's mnBestInliers / mvbBestInliers.  Returns a dict:
+    n_consumed, returned, best, best_inliers_out; best_Tcw and best_mask (None where best is -1); refined_Tcw, refined_inliers, refined_mask (None where
+    returned is -1); with per_hypothesis also hyp_R, hyp_t (float64), hyp_count, hyp_mask of every hypothesis and ref_hyp, ref_R, ref_t, ref_count,
+    ref_mask of every refined candidate."""
+    return pnp_iterate_batch([dict(K=K, corr=corr, quads=quads, min_inliers=min_inliers, best_in=best_in, best_mask_in=best_mask_in)],
+                             per_hypothesis=per_hypothesis, library=library, device=device, _single=True)[0]
+
+
+def pnp_iterate_batch(problems, per_hypothesis=False, library=None, device=None, _single=False):
+    """Independent solvers in one device call (orbhip_pnp_iterate_batch): problems is a sequence of dicts with the keyword names of pnp_iterate.
+    Returns a list of result dicts."""
+    n = len(problems)
+    arr = (_PnpProblem * max(n, 1))()
+    keep = [_pnp_fill(arr[k], q, per_hypothesis) for k, q in enumerate(problems)]
+    L = lib(library)
+    if _single:
+        _check(L.orbhip_pnp_iterate(0 if device is None else device, C.cast(arr, C.c_void_p)), "orbhip_pnp_iterate", L)
+    else:
+        _check(L.orbhip_pnp_iterate_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_pnp_iterate_batch", L)
+    return [_pnp_result(arr[k], keep[k]) for k in range(n)]
 
 
 def nn_expanded_size(ndb, library=None):
