@@ -2,7 +2,8 @@
 with pixel noise that grows with the level, a share of the matches wrong.  Everything is a pure function of the parameters and a seed.
 
 Graded sizes are where a wave, a mask word or a clamp of SetRansacParameters turns over: n = 4 and 5 (N == mRansacMinInliers: one iteration), 20, 63,
-64, 65, 129, 300, 1000; 1, 5 and 300 hypotheses; one planar scene (all points on a wall: ABt of estimate_R_and_t has rank 2)."""
+64, 65, 129, 300, 1000; 1, 5 and 300 hypotheses; one planar scene (all points on a wall; no hypothesis of it reaches the minimum, so nothing is refined
+and ABt of estimate_R_and_t never has rank 2 there: the planar refines are planar_exact and planar_failing_refines of REFINE_CASES)."""
 import numpy as np
 
 import pnp_model as M
@@ -196,9 +197,57 @@ CASES = [("n4_h1",        4,    1,    11,   0.0,    0.0,   4,         0.5,    Fa
          ("planar_n100_h5", 100, 5,   21,   0.2,    0.3,   10,        0.5,    True)]
 ALL_NAMES = [c[0] for c in CASES]
 
+# Cases whose hypotheses reach the minimum, so that k_pnp_refine runs on masks of 3, 5, 16 and 65 words (none of the eleven above refines past one bit
+# of a second word), and planar sets that reach the refine: exact (ABt has rank 2, the pose is finite) and noisy (det < 0 is flipped, every refine
+# fails).  With them go first_in_word1 and planar_lattice below.  tests/pnp_checks.py (check_refine_case) asserts from the model what each must provide.
+REFINE_CASES = [("refine_n129",  129,  20,   49,   0.2,    0.3,   10,        0.5,    False),      # (seed 41 leaves bit 128, the third word's only one, clear)
+                ("refine_n300",  300,  20,   42,   0.2,    0.3,   10,        0.5,    False),
+                ("refine_n1000", 1000, 20,   43,   0.2,    0.3,   10,        0.5,    False),
+                ("refine_n4160", 4160, 6,    48,   0.2,    0.3,   10,        0.5,    False),
+                ("planar_exact", 100,  40,   45,   0.0,    0.0,   10,        0.5,    True),
+                ("planar_failing_refines", 200, 40, 46, 0.1, 0.3, 10,        0.5,    True)]
+REFINE_NAMES = [c[0] for c in REFINE_CASES] + ["refine_first_in_word1", "planar_lattice"]
+
+
+def first_in_word1():
+    """200 correspondences of which the first 70 are wrong and no hypothesis draws them: every mask a refine takes starts in its second word"""
+    corr, Rcw, tcw, _ = scene(200, 47, 0.1, 0.3)
+    rng = np.random.default_rng(1)
+    corr[:70, 3], corr[:70, 4] = rng.uniform(0.0, W, 70).astype(f32), rng.uniform(0.0, H, 70).astype(f32)
+    return corr, (70 + draw_quads(130, 20, 47)).astype(np.int32), 60, Rcw, tcw
+
+
+def planar_lattice(n=100, nh=10, seed=0):
+    """Points that float32 holds exactly on one world plane, z = 5 + x / 4 + y / 2 with x, y multiples of 1 / 256, seen without noise: the smallest
+    eigenvalue of PW0^T PW0 is rounding alone, so the stated Jacobi returns it below zero about as often as above.  Below zero it is clamped, the third
+    control point falls on the centroid, CC is singular and the pose not finite; scene(planar=True) never gets there in a refine,
+    because rounding its world points to float32 lifts them off their wall by more than the eigen-solver's error."""
+    rng = np.random.default_rng(seed)
+    Rcw, tcw = pose(rng)
+    fx, fy, cx, cy = [float(k) for k in K]
+    xy = rng.integers(-384, 385, (n, 2)).astype(np.float64) / 256.0
+    Xw = np.stack([xy[:, 0], xy[:, 1], 5.0 + xy[:, 0] / 4.0 + xy[:, 1] / 2.0], 1)
+    assert np.array_equal(Xw.astype(f32).astype(np.float64), Xw)
+    Pc = Xw @ Rcw.T + tcw
+    corr = np.zeros((n, 6), f32)
+    corr[:, 0:3], corr[:, 3], corr[:, 4] = Xw.astype(f32), (cx + fx * Pc[:, 0] / Pc[:, 2]).astype(f32), (cy + fy * Pc[:, 1] / Pc[:, 2]).astype(f32)
+    corr[:, 5] = M.max_errors(np.ones(n, f32), TH2)
+    return corr, draw_quads(n, nh, seed), M.ransac_parameters(n, 0.99, 10, 300, 4, 0.5)[0], Rcw, tcw
+
 
 def case(name):
     """(corr, quads, min_inliers, Rcw, tcw)"""
     _, n, nh, seed, outliers, noise, mi, eps, planar = CASES[ALL_NAMES.index(name)]
+    corr, Rcw, tcw, _ = scene(n, seed, outliers, noise, planar)
+    return corr, draw_quads(n, nh, seed), M.ransac_parameters(n, 0.99, mi, 300, 4, eps)[0], Rcw, tcw
+
+
+def refine_case(name):
+    """(corr, quads, min_inliers, Rcw, tcw) of one of REFINE_NAMES"""
+    if name == "refine_first_in_word1":
+        return first_in_word1()
+    if name == "planar_lattice":
+        return planar_lattice(100, 10, 68)
+    _, n, nh, seed, outliers, noise, mi, eps, planar = REFINE_CASES[REFINE_NAMES.index(name)]
     corr, Rcw, tcw, _ = scene(n, seed, outliers, noise, planar)
     return corr, draw_quads(n, nh, seed), M.ransac_parameters(n, 0.99, mi, 300, 4, eps)[0], Rcw, tcw

@@ -94,6 +94,11 @@ def check_conditions():
         several += len(m["ref_hyp"]) > 1
         bad += int((~(np.isfinite(m["hyp_R"]).all(axis=(1, 2)) & np.isfinite(m["hyp_t"]).all(axis=1))).sum())
         total += len(m["hyp_count"])
+    for name in Cs.REFINE_NAMES:                                                # the cases of check_refine_case count too, under the same cap
+        m = refine_case(name)[3]
+        bad += int((~(np.isfinite(m["hyp_R"]).all(axis=(1, 2)) & np.isfinite(m["hyp_t"]).all(axis=1))).sum())
+        total += len(m["hyp_count"])
+    print(f"{bad} non-finite hypotheses of {total}")
     assert refined >= 1 and exhausted >= 1 and never >= 1 and several >= 1, (refined, exhausted, never, several)
     assert bad < 0.05 * total, (bad, total)
 
@@ -317,6 +322,202 @@ def check_jacobi_forms(library):
         L.orbhip_test_jacobi12(A.ctypes.data, out.ctypes.data)
         assert same_bits(np.diag(out[0]).copy(), np.diag(out[2]).copy()) and same_bits(out[1], out[3]), k
         assert same_bits(np.diag(out[0]).copy(), w[k]) and same_bits(out[1], V[k]), k
+
+
+# ------------------------------------------------------------------------------------------------ refines past one mask word, planar refines
+def refine_case(name):
+    """(corr, quads, min_inliers, the model's answer, the arms the model took: trace["hyp"] and trace["ref"]) of one of Cs.REFINE_NAMES"""
+    key = ("refine", name)
+    if key not in _cache:
+        corr, quads, mi, _, _ = Cs.refine_case(name)
+        trace = {}
+        m = M.iterate(Cs.K, corr, quads, mi, trace=trace)
+        for a in [corr, quads] + [v for v in m.values() if isinstance(v, np.ndarray)]:
+            a.setflags(write=False)
+        _cache[key] = (corr, quads, mi, m, trace)
+    return _cache[key]
+
+
+def _lowest_bit(words):
+    nz = np.flatnonzero(words)
+    return 64 * int(nz[0]) + (int(words[nz[0]]) & -int(words[nz[0]])).bit_length() - 1 if len(nz) else -1
+
+
+def check_refine_case(name, library):
+    """k_pnp_refine where the graded cases never take it: masks of 3, 5, 16 and 65 words with set bits in every word (the masked sum's stride past two
+    passes, the popcount loop's second pass), a mask whose first set bit is in its second word, and planar sets in a refine: rank 2 with a finite pose,
+    det < 0, the clamped eigenvalue.  What each case must provide is asserted from the model first."""
+    corr, quads, mi, m, trace = refine_case(name)
+    words, ref = (len(corr) + 63) // 64, trace["ref"]
+    src = [m["hyp_mask"][h] for h in m["ref_hyp"] if h >= 0]                    # the masks the refines ran over
+    assert len(m["ref_hyp"]) >= 1 and len(src) == len(m["ref_hyp"]) and ref.get("words_%d" % words, 0) == len(src), (name, m["ref_hyp"], ref)
+    if name.startswith("refine_n"):
+        assert m["returned"] >= 0 and all((s != 0).all() for s in src), (name, m["returned"], src)
+        assert words == {"refine_n129": 3, "refine_n300": 5, "refine_n1000": 16, "refine_n4160": 65}[name]
+    elif name == "refine_first_in_word1":
+        assert all(s[0] == 0 and _lowest_bit(s) >= 64 for s in src) and ref.get("first_ge_64", 0) == len(src) and m["returned"] >= 0, (name, src)
+    elif name == "planar_exact":
+        # ABt of a refine has rank 2 and the pose is finite; the clamp is met by minimal sets only (their poses are the non-finite ones)
+        assert m["returned"] >= 0 and ref.get("rank2_finite", 0) >= 1 and np.isfinite(m["ref_R"]).all() and np.isfinite(m["ref_t"]).all(), (name, ref)
+        assert trace["hyp"].get("dc_clamp", 0) >= 1 and trace["hyp"].get("rank2_finite", 0) >= 1, (name, trace["hyp"])
+    elif name == "planar_failing_refines":
+        assert len(src) >= 2 and (m["ref_count"] <= mi).all() and m["returned"] == -1 and m["best"] >= 0 and ref.get("det_negative", 0) >= 1, (name, m["ref_count"], ref)
+    elif name == "planar_lattice":
+        # the clamp inside a refine: CC is singular, the refined pose not finite, the refine fails with no inlier
+        assert ref.get("dc_clamp", 0) >= 1 and np.isnan(m["ref_R"]).all() and np.isnan(m["ref_t"]).all() and (m["ref_count"] == 0).all() and m["returned"] == -1 and m["best"] >= 0, (name, ref)
+    d = device(corr, quads, mi, library=library)
+    print(f"{name}: n {len(corr)}, {words} words, {len(quads)} hypotheses, min {mi}, returned {d['returned']}, best {d['best']}, refines of {[int(h) for h in d['ref_hyp']]}: "
+          f"{[int(np.unpackbits(s.view(np.uint8)).sum()) for s in src]} -> {[int(c) for c in d['ref_count']]} inliers; arms in the refines {ref}")
+    assert differences(d, m) == [], name
+
+
+def sign_first():
+    """the two-pose scene with pose A's lowest point mirrored through the camera centre of the hypothesis, and the same with that point and the next
+    swapped: (i, corr, quad, model answer, corr swapped, quad swapped, model answer)"""
+    if "sign_first" not in _cache:
+        T = Cs.two_poses()
+        quad, mi = list(T["quad_a"]), T["mi"]
+        i = int(np.flatnonzero(T["is_a"])[0])
+        assert i not in quad and i + 1 < len(T["corr"]) and T["is_a"][i + 1]
+        m0 = model(T["corr"], [quad], mi)
+        R, t = m0["hyp_R"][0], m0["hyp_t"][0]
+        corr = T["corr"].copy()
+        Pc = R @ corr[i, 0:3].astype(np.float64) + t
+        corr[i, 0:3] = (R.T @ (-Pc - t)).astype(f32)
+        swapped = corr.copy()
+        swapped[[i, i + 1]] = corr[[i + 1, i]]
+        quad_s = [i if q == i + 1 else q for q in quad]
+        tr, tr_s = {}, {}
+        m, ms = M.iterate(Cs.K, corr, [quad], mi, trace=tr), M.iterate(Cs.K, swapped, [quad_s], mi, trace=tr_s)
+        _cache["sign_first"] = (i, corr, quad, m, tr, swapped, quad_s, ms, tr_s)
+    return _cache["sign_first"]
+
+
+def check_sign_first(library):
+    """solve_for_sign reads the FIRST point of the set only.  The first set bit of the refined mask is a point behind the camera: the refine flips the
+    sign and finds no inlier; with that point second, the same set refines well.  A kernel that took any other set bit as `first` fails one of the two."""
+    i, corr, quad, m, tr, swapped, quad_s, ms, tr_s = sign_first()
+    mi = Cs.two_poses()["mi"]
+    assert _lowest_bit(m["hyp_mask"][0]) == i and _lowest_bit(ms["hyp_mask"][0]) == i and (int(ms["hyp_mask"][0][0]) >> (i + 1)) & 1
+    assert list(m["ref_hyp"]) == [0] and list(ms["ref_hyp"]) == [0] and m["ref_count"][0] != ms["ref_count"][0], (m["ref_count"], ms["ref_count"])
+    assert tr["ref"].get("sign_depends_on_first", 0) >= 1 and tr_s["ref"].get("sign_depends_on_first", 0) >= 1, (tr["ref"], tr_s["ref"])
+    assert (m["returned"] >= 0) != (ms["returned"] >= 0), (m["returned"], ms["returned"])
+    print(f"first set bit {i}: mirrored point first: refined {m['ref_count'][0]}, returned {m['returned']}; second: refined {ms['ref_count'][0]}, returned {ms['returned']} (min {mi})")
+    assert differences(device(corr, [quad], mi, library=library), m) == []
+    assert differences(device(swapped, [quad_s], mi, library=library), ms) == []
+
+
+PASS_SEQUENCES = ("lane63_then_lane0", "tie_in_pass1", "carried_in_pass1_then_new", "new_before_carried", "carried_never_reached", "returns_on_carried_in_pass1")
+
+
+def pass_sequence(name):
+    """a hypothesis sequence of the two-pose scene longer than one 64-lane pass of k_pnp_select: (quads, best_in, best_mask_in, the model's answer, the
+    bookkeeping the model must show)"""
+    key = ("pass", name)
+    if key not in _cache:
+        T = Cs.two_poses()
+        J, B0, B1, A, mi = T["quad_junk"], T["quads_b"][0], T["quads_b"][1], T["quad_a"], T["mi"]
+        if "first" not in _cache:
+            _cache["first"] = model(T["corr"], [B0], mi)                        # a call that ended on B's unrefined mask: count mi
+            _cache["after"] = model(T["corr"], [A], mi)                         # a call that returned on A: A's count and mask stay in the solver
+        first, after = _cache["first"], _cache["after"]
+        assert first["best"] == 0 and first["returned"] == -1 and first["best_inliers_out"] == mi
+        assert after["returned"] == 0 and after["best"] == 0 and after["best_inliers_out"] > mi
+        quads, carried, want = {
+            # a new maximum at lane 63 whose refine fails (count == min), the next at lane 0 of pass 1
+            "lane63_then_lane0": ([J] * 63 + [B0, A], None, dict(ref_hyp=[63, 64], returned=64, n_consumed=65, best=64)),
+            # a tie in pass 1 refines the standing mask again and adds no candidate
+            "tie_in_pass1": ([J] * 10 + [B0] + [J] * 60 + [B1] + [J] * 5, None, dict(ref_hyp=[10], returned=-1, n_consumed=77, best=10)),
+            # the carried-in mask first met in pass 1, a new maximum in pass 2
+            "carried_in_pass1_then_new": ([J] * 70 + [B1] + [J] * 59 + [A] + [J] * 3, first, dict(ref_hyp=[-1, 130], returned=130, n_consumed=131, best=130)),
+            # a new maximum comes first: the carried-in mask is never refined
+            "new_before_carried": ([J] * 130 + [A, B1], first, dict(ref_hyp=[130], returned=130, n_consumed=131, best=130)),
+            "carried_never_reached": ([J] * 65, first, dict(ref_hyp=[], returned=-1, n_consumed=65, best=-1, best_inliers_out=mi)),
+            # the carried-in mask first met in pass 1 and its refine succeeds: the call returns at cand_at[0], which none of the others reads
+            "returns_on_carried_in_pass1": ([J] * 70 + [A] + [J] * 3, after, dict(ref_hyp=[-1], returned=70, n_consumed=71, best=-1)),
+        }[name]
+        best_in, mask_in = (0, None) if carried is None else (carried["best_inliers_out"], carried["best_mask"])
+        _cache[key] = (quads, best_in, mask_in, model(T["corr"], quads, mi, best_in, mask_in), want)
+    return _cache[key]
+
+
+def check_select_passes(name, library):
+    """k_pnp_select past its first 64 hypotheses (PASS_SEQUENCES): the model's bookkeeping is asserted first, then the device must give the model's bits"""
+    T = Cs.two_poses()
+    quads, best_in, mask_in, m, want = pass_sequence(name)
+    assert len(quads) > 64 and all(list(m[k]) == want[k] if k == "ref_hyp" else m[k] == want[k] for k in want), ({k: m[k] for k in want}, want)
+    if name == "tie_in_pass1":
+        assert (m["hyp_count"][[10, 71]] == T["mi"]).all()
+    d = device(T["corr"], quads, T["mi"], best_in, mask_in, library=library)
+    assert differences(d, m) == [], name
+    if name == "carried_never_reached":
+        assert d["best_Tcw"] is None and d["best_mask"] is None and len(d["ref_hyp"]) == 0
+
+
+def _raw_call(library, problem, change):
+    """orbhip_pnp_iterate on a record filled by OH._pnp_fill and then changed by change(rec, keep): (rec, keep)"""
+    rec = (OH._PnpProblem * 1)()
+    keep = OH._pnp_fill(rec[0], problem, True)
+    change(rec[0], keep)
+    assert OH.lib(library).orbhip_pnp_iterate(0, C.cast(rec, C.c_void_p)) == 0
+    return rec[0], keep
+
+
+REF_KEYS = ("ref_hyp", "ref_R", "ref_t", "ref_count", "ref_mask")
+
+
+def check_ref_cap(library):
+    """a caller with room for fewer refine records than the loop made: n_ref says how many there were, only ref_cap rows are written"""
+    T, quads, m = rules_sequence()
+    assert len(m["ref_hyp"]) == 2
+    fill = dict(ref_hyp=-7, ref_R=7.5, ref_t=7.5, ref_count=-7, ref_mask=0x7777777777777777)
+
+    def change(rec, keep):
+        rec.ref_cap = 1
+        for k in REF_KEYS:
+            keep[k][...] = fill[k]
+
+    rec, keep = _raw_call(library, dict(K=Cs.K, corr=T["corr"], quads=quads, min_inliers=T["mi"]), change)
+    assert rec.n_ref == 2
+    for k in REF_KEYS:
+        assert same_bits(keep[k][0], np.asarray(m[k][0])), k
+        assert (keep[k][1:] == fill[k]).all(), k
+    d = OH._pnp_result(rec, keep)
+    assert differences(d, {k: v for k, v in m.items() if k not in REF_KEYS}) == []
+
+
+def check_hyp_count_alone(library):
+    """a caller that asks for the counts of the hypotheses and not for their poses or masks"""
+    T, quads, m = rules_sequence()
+
+    def change(rec, keep):
+        rec.hyp_R, rec.hyp_t, rec.hyp_mask = None, None, None
+        keep["hyp_R"][...], keep["hyp_t"][...], keep["hyp_mask"][...] = 7.5, 7.5, 0x7777777777777777
+
+    rec, keep = _raw_call(library, dict(K=Cs.K, corr=T["corr"], quads=quads, min_inliers=T["mi"]), change)
+    assert (keep["hyp_R"] == 7.5).all() and (keep["hyp_t"] == 7.5).all() and (keep["hyp_mask"] == 0x7777777777777777).all()
+    assert np.array_equal(keep["hyp_count"], m["hyp_count"])
+    d = OH._pnp_result(rec, keep)
+    assert differences(d, {k: v for k, v in m.items() if k not in ("hyp_R", "hyp_t", "hyp_mask")}) == []
+
+
+def check_batch_refines(library):
+    """the new problems in one call, in both orders: different hypothesis counts, candidate counts and mask words, so that surplus blocks of k_pnp_hyp and
+    k_pnp_refine return early; every slot gives its single call's bits"""
+    T = Cs.two_poses()
+    probs = []
+    for name in ("refine_n129", "planar_exact", "refine_first_in_word1", "planar_lattice"):
+        corr, q, mi, m, _ = refine_case(name)
+        probs.append((dict(K=Cs.K, corr=corr, quads=q, min_inliers=mi), m))
+    quads, best_in, mask_in, m, _ = pass_sequence("carried_in_pass1_then_new")
+    probs.insert(3, (dict(K=Cs.K, corr=T["corr"], quads=quads, min_inliers=T["mi"], best_in=best_in, best_mask_in=mask_in), m))
+    _, corr, quad, m = sign_first()[:4]
+    probs.append((dict(K=Cs.K, corr=corr, quads=[quad], min_inliers=T["mi"]), m))
+    assert len({len(p[0]["quads"]) for p in probs}) >= 4 and len({len(p[1]["ref_hyp"]) for p in probs}) >= 2 and len({p[1]["hyp_mask"].shape[1] for p in probs}) >= 3
+    for order in (list(range(len(probs))), list(range(len(probs)))[::-1]):
+        res = orb_slam2_amd.pnp_iterate_batch([probs[k][0] for k in order], per_hypothesis=True, library=library)
+        for k, d in zip(order, res):
+            assert differences(d, probs[k][1]) == [], (order, k)
 
 
 # ------------------------------------------------------------------------------------------------ the C++ drop-in

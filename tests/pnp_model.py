@@ -67,6 +67,13 @@ def jacobi_batch(A):
     return A[:, np.arange(n), np.arange(n)].copy(), V
 
 
+def note(trace, arm):
+    """count one passage through the named arm in `trace` (a dict, or None: nothing is recorded).  A trace changes no arithmetic: tests/pnp_checks.py asks
+    it which arms a case reached, so that no test passes by emptiness"""
+    if trace is not None:
+        trace[arm] = trace.get(arm, 0) + 1
+
+
 def sort_desc(w):
     """indices of w in descending order by insertion with a strict `>`: equal values keep their index order"""
     o = list(range(len(w)))
@@ -208,7 +215,7 @@ def cross(a, b):
     return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
 
 
-def hestenes(abt):
+def hestenes(abt, trace=None):
     """U, sigma, V of the 3 x 3 ABt = U diag(sigma) V^T by one-sided Jacobi: columns of G = ABt W made orthogonal pair by pair; sorted descending;
     at rank 2 (sigma_3 <= RANK_TOL sigma_1) the third columns are the cross products of the first two"""
     G = [np.array(abt[:, c], f64) for c in range(3)]
@@ -240,13 +247,16 @@ def hestenes(abt):
     U = [G[o[c]] / sg[o[c]] for c in range(3)]
     V = [W[o[c]] for c in range(3)]
     if not sg[o[2]] > RANK_TOL * sg[o[0]]:
+        note(trace, "rank2_finite" if np.isfinite(sg).all() and sg[o[1]] > 0.0 else "rank2_degenerate")
         U[2], V[2] = cross(U[0], U[1]), cross(V[0], V[1])
+    else:
+        note(trace, "full_rank")
     return np.array(U).T, np.array([sg[k] for k in o]), np.array(V).T
 
 
-def rotation(abt):
+def rotation(abt, trace=None):
     """estimate_R_and_t's R = U V^T with the det < 0 row flip; 3 x 3"""
-    U, _, V = hestenes(abt)
+    U, _, V = hestenes(abt, trace)
     R = np.zeros((3, 3))
     for i in range(3):
         for j in range(3):
@@ -254,6 +264,7 @@ def rotation(abt):
     det = ((((((R[0, 0] * R[1, 1]) * R[2, 2] + (R[0, 1] * R[1, 2]) * R[2, 0]) + (R[0, 2] * R[1, 0]) * R[2, 1]) - (R[0, 2] * R[1, 1]) * R[2, 0]) -
             (R[0, 1] * R[1, 0]) * R[2, 2]) - (R[0, 0] * R[1, 2]) * R[2, 1])
     if det < 0.0:
+        note(trace, "det_negative")
         R[2] = -R[2]
     return R
 
@@ -262,7 +273,7 @@ def rotation(abt):
 PA, PB = (0, 0, 0, 1, 1, 2), (1, 2, 3, 2, 3, 3)
 
 
-def control_points(c0, w, V, dm):
+def control_points(c0, w, V, dm, trace=None):
     """choose_control_points from the eigenvalues w and eigenvectors V (columns) of PW0^T PW0: the centroid, then c0 + sqrt(dc / n) * vector in descending
     order of dc; an eigenvalue below zero (rounding, on coplanar points) is clamped to 0 before the square root"""
     o = sort_desc(w)
@@ -271,13 +282,14 @@ def control_points(c0, w, V, dm):
     for i in range(1, 4):
         dc = w[o[i - 1]]
         if dc < 0.0:
+            note(trace, "dc_clamp")
             dc = f64(0.0)
         k = np.sqrt(dc / dm)
         cws[i] = c0 + k * V[:, o[i - 1]]
     return cws
 
 
-def epnp_front(S, K):
+def epnp_front(S, K, trace=None):
     """choose_control_points, compute_barycentric_coordinates and M^T M: the state compute_pose carries to the 12 x 12 eigenproblem"""
     fu, fv, uc, vc = [f64(f32(k)) for k in K]
     dm = f64(S.m)
@@ -285,7 +297,7 @@ def epnp_front(S, K):
     d = S.P - c0
     s6 = reduce(S.valid, np.stack([d[:, 0] * d[:, 0], d[:, 0] * d[:, 1], d[:, 0] * d[:, 2], d[:, 1] * d[:, 1], d[:, 1] * d[:, 2], d[:, 2] * d[:, 2]], 1))
     w, V = jacobi_batch(np.array([[[s6[0], s6[1], s6[2]], [s6[1], s6[3], s6[4]], [s6[2], s6[4], s6[5]]]]))
-    cws = control_points(c0, w[0], V[0], dm)
+    cws = control_points(c0, w[0], V[0], dm, trace)
     cc = np.zeros(9)
     for i in range(3):
         for j in range(1, 4):
@@ -307,7 +319,7 @@ def epnp_front(S, K):
     return dict(S=S, K=(fu, fv, uc, vc), dm=dm, c0=c0, cws=cws, ci=ci, a=a, MtM=MtM)
 
 
-def epnp_back(st, w, V):
+def epnp_back(st, w, V, trace=None):
     """compute_pose from the eigenvectors on: R (3 x 3), t (3,) in double"""
     S, (fu, fv, uc, vc), dm, c0, cws, a = st["S"], st["K"], st["dm"], st["c0"], st["cws"], st["a"]
     o = sort_desc(w)
@@ -333,13 +345,17 @@ def epnp_back(st, w, V):
                 ccs[j, k] = s
         if S.m > 0:
             af = a[S.first]
+            if trace is not None:                                               # would another member of the set have decided otherwise?
+                neg = (((a[:, 0] * ccs[0, 2] + a[:, 1] * ccs[1, 2]) + a[:, 2] * ccs[2, 2]) + a[:, 3] * ccs[3, 2] < 0.0)[S.valid]
+                note(trace, "sign_depends_on_first" if neg.any() and not neg.all() else "sign_unanimous")
             if ((af[0] * ccs[0, 2] + af[1] * ccs[1, 2]) + af[2] * ccs[2, 2]) + af[3] * ccs[3, 2] < 0.0:
+                note(trace, "sign_flip")
                 ccs = -ccs
         pcs = np.stack([((a[:, 0] * ccs[0, j] + a[:, 1] * ccs[1, j]) + a[:, 2] * ccs[2, j]) + a[:, 3] * ccs[3, j] for j in range(3)], 1)
         pc0 = reduce(S.valid, pcs) / dm
         wd = S.P - c0
         abt = reduce(S.valid, np.stack([(pcs[:, j] - pc0[j]) * wd[:, c] for j in range(3) for c in range(3)], 1)).reshape(3, 3)
-        R = rotation(abt)
+        R = rotation(abt, trace)
         t = np.array([pc0[i] - dot3(R[i], c0) for i in range(3)])
         P = S.P
         Xc = ((R[0, 0] * P[:, 0] + R[0, 1] * P[:, 1]) + R[0, 2] * P[:, 2]) + t[0]
@@ -353,18 +369,18 @@ def epnp_back(st, w, V):
     return best[1], best[2]
 
 
-def epnp_many(sets, K):
+def epnp_many(sets, K, trace=None):
     """compute_pose for several sets (the 12 x 12 eigenproblems run in lockstep): a list of (R, t)"""
     with np.errstate(all="ignore"):
-        fronts = [epnp_front(S, K) for S in sets]
+        fronts = [epnp_front(S, K, trace) for S in sets]
         if not fronts:
             return []
         w, V = jacobi_batch(np.array([st["MtM"] for st in fronts]))
-        return [epnp_back(st, w[h], V[h]) for h, st in enumerate(fronts)]
+        return [epnp_back(st, w[h], V[h], trace) for h, st in enumerate(fronts)]
 
 
-def epnp(corr, K, quad=None, mask=None):
-    return epnp_many([Set(corr, quad, mask)], K)[0]
+def epnp(corr, K, quad=None, mask=None, trace=None):
+    return epnp_many([Set(corr, quad, mask)], K, trace)[0]
 
 
 # ------------------------------------------------------------------------------------------------ CheckInliers
@@ -407,8 +423,9 @@ def tcw(R, t):
 
 
 # ------------------------------------------------------------------------------------------------ iterate
-def iterate(K, corr, quads, min_inliers, best_in=0, best_mask_in=None):
-    """what orbhip_pnp_iterate returns, from the model: a dict with the ABI's names (hyp_* for every hypothesis, ref_* for every refine the loop made)"""
+def iterate(K, corr, quads, min_inliers, best_in=0, best_mask_in=None, trace=None):
+    """what orbhip_pnp_iterate returns, from the model: a dict with the ABI's names (hyp_* for every hypothesis, ref_* for every refine the loop made).
+    `trace`, a dict, receives the arms taken: trace["hyp"] counts those of the hypotheses, trace["ref"] those of the refines (see note)"""
     corr = np.asarray(corr, f32).reshape(-1, 6)
     quads = np.asarray(quads, np.int32).reshape(-1, 4)
     n, nh, mi = len(corr), len(quads), int(min_inliers)
@@ -418,7 +435,8 @@ def iterate(K, corr, quads, min_inliers, best_in=0, best_mask_in=None):
     words = (n + 63) // 64
     hR, ht, hc, hm = np.zeros((nh, 3, 3)), np.zeros((nh, 3)), np.zeros(nh, np.int32), np.zeros((nh, words), np.uint64)
     masks = []
-    for h, (R, t) in enumerate(epnp_many([Set(corr, q) for q in quads], K)):
+    t_hyp, t_ref = (None, None) if trace is None else (trace.setdefault("hyp", {}), trace.setdefault("ref", {}))
+    for h, (R, t) in enumerate(epnp_many([Set(corr, q) for q in quads], K, t_hyp)):
         m, c = check_inliers(R, t, K, corr)
         hR[h], ht[h], hc[h], hm[h] = R, t, c, pack_mask(m)
         masks.append(m)
@@ -430,7 +448,10 @@ def iterate(K, corr, quads, min_inliers, best_in=0, best_mask_in=None):
             if hc[h] > run:
                 run, cur, best = int(hc[h]), h, h
             if cur not in refs:                                                 # Refine() is a pure function of the best mask
-                R, t = epnp(corr, K, mask=carried if cur < 0 else masks[cur])
+                src = carried if cur < 0 else masks[cur]
+                note(t_ref, "words_%d" % words)
+                note(t_ref, "first_ge_64" if src.any() and int(np.flatnonzero(src)[0]) >= 64 else "first_lt_64")
+                R, t = epnp(corr, K, mask=src, trace=t_ref)
                 refs[cur] = (R, t) + check_inliers(R, t, K, corr)
             if refs[cur][3] > mi:
                 returned, consumed = h, h + 1

@@ -55,6 +55,32 @@ def test_batch_slots_give_the_same_bits(emu_lib):
     K.check_batch_slots(emu_lib)
 
 
+@pytest.mark.parametrize("name", Cs.REFINE_NAMES)
+def test_refine_equals_model(emu_lib, name):
+    K.check_refine_case(name, emu_lib)
+
+
+def test_sign_rule_reads_the_first_set_bit(emu_lib):
+    K.check_sign_first(emu_lib)
+
+
+@pytest.mark.parametrize("name", K.PASS_SEQUENCES)
+def test_selection_across_passes(emu_lib, name):
+    K.check_select_passes(name, emu_lib)
+
+
+def test_fewer_refine_rows_than_refines(emu_lib):
+    K.check_ref_cap(emu_lib)
+
+
+def test_hypothesis_counts_alone(emu_lib):
+    K.check_hyp_count_alone(emu_lib)
+
+
+def test_batch_of_refining_problems(emu_lib):
+    K.check_batch_refines(emu_lib)
+
+
 def test_repeated_call_gives_the_same_bits(emu_lib):
     K.check_repeat(emu_lib)
 

@@ -45,6 +45,32 @@ def test_batch_slots_give_the_same_bits(gpu_lib):
     K.check_batch_slots(gpu_lib)
 
 
+@pytest.mark.parametrize("name", Cs.REFINE_NAMES)
+def test_refine_equals_model(gpu_lib, name):
+    K.check_refine_case(name, gpu_lib)
+
+
+def test_sign_rule_reads_the_first_set_bit(gpu_lib):
+    K.check_sign_first(gpu_lib)
+
+
+@pytest.mark.parametrize("name", K.PASS_SEQUENCES)
+def test_selection_across_passes(gpu_lib, name):
+    K.check_select_passes(name, gpu_lib)
+
+
+def test_fewer_refine_rows_than_refines(gpu_lib):
+    K.check_ref_cap(gpu_lib)
+
+
+def test_hypothesis_counts_alone(gpu_lib):
+    K.check_hyp_count_alone(gpu_lib)
+
+
+def test_batch_of_refining_problems(gpu_lib):
+    K.check_batch_refines(gpu_lib)
+
+
 def test_repeated_call_gives_the_same_bits(gpu_lib):
     K.check_repeat(gpu_lib)
 
