@@ -329,6 +329,45 @@ orbhip_status orbhip_pnp_iterate(int device, orbhip_pnp_problem* problem);
 /* one round of Tracking::Relocalization's candidate loop: independent solvers of any mix of sizes */
 orbhip_status orbhip_pnp_iterate_batch(int device, int nproblems, orbhip_pnp_problem* problems);
 
+/* Initializer::Initialize (Initializer.cc:44-121): monocular initialisation from n matches between a reference and a current frame - both RANSACs
+   (FindHomography, FindFundamental over the same n_sets minimal sets of 8), the model choice RH = SH / (SH + SF) > 0.40, ReconstructH or
+   ReconstructF with CheckRT and Triangulate for each of the 8 or 4 motion hypotheses, and the selection rules, in one call: one upload, one
+   download, four launches, no host decision in between.  The caller draws the sets (`sets`: 8 indices per set, each in 0..n-1, as the reference's
+   swap-remove draw gives them) and runs Normalize's two serial float passes over ALL key points of each frame: norm1 / norm2 are meanX, meanY, sX, sY.
+   matches holds u1, v1, u2, v2 of pair i in mvMatches12 order.  The arithmetic is DESIGN.md H19, restated in tests/init_model.py; gemm_mode is H11's
+   (0 or 1); mode 2 is ORBHIP_ERR_UNSUPPORTED.  min_parallax and min_triangulated are ReconstructH / F's (1.0 and 50 in Initialize).
+   Outputs: returned (0 or 1); model (0: H chosen, 1: F chosen, -1: the chosen model has no hypothesis with a score above 0 - the call returns false
+   where the reference would hand an empty Mat on); best_h / best_f the winning set of each model (-1: none), SH, SF, H21, F21 (zero without a
+   winner), mask_h / mask_f (n bytes each); n_mot motion hypotheses were checked (8, 4, or 0: none chosen, or ReconstructH's d1/d2, d2/d3 return),
+   mot_good their nGood, mot_cos the cosine at index min(50, nGood - 1) of each one's sorted accepted cosines (0 with nGood = 0), best_mot the
+   hypothesis the selection rules ended on (-1: none); with returned = 1 R21, t21 (else zero), and PER MATCH p3d (3 n) and triangulated (n bytes):
+   what the reference leaves in vP3D / vbTriangulated at mvMatches12[i].first, 0 where it assigns nothing or returns false.
+   Optional outputs (NULL: skipped): hyp_score 2 n_sets and hyp_M 18 n_sets - every H hypothesis, then every F hypothesis; mot_R 72 and mot_t 24
+   (rows from n_mot on are zero).
+   n below 8 or above 8192, n_sets outside 1..4096, an index outside 0..n-1, a NULL matches / sets / mask_h / mask_f / p3d / triangulated:
+   ORBHIP_ERR_INVALID, nothing computed and nothing written.  Results repeat bit for bit and do not depend on a problem's place in a batch.
+   Re-entrant like the Sim3 and PnP entries.
+   PRECONDITION on the host's C library: CheckRT's parallax, (float)(acosf(c) * 180 / CV_PI), never runs on the device.  The host finds, by bisection
+   over the floats of [-1, 1], the largest cosine whose parallax passes `> min_parallax` and the largest that passes `>= min_parallax`, and the device
+   compares the statistic's cosine with them.  That is the reference's comparison exactly when acosf does not rise anywhere on [-1, 1] (a correctly
+   rounded acosf, and every monotone one, qualifies); a C library whose acosf rises between two neighbouring floats near the threshold could decide a
+   cosine between them the other way. */
+typedef struct {
+    float K[4];                 /* fx, fy, cx, cy */
+    float sigma;
+    float norm1[4], norm2[4];   /* meanX, meanY, sX, sY of Normalize over mvKeys1 / mvKeys2 */
+    const float* matches; int32_t n;
+    const int32_t* sets; int32_t n_sets;
+    float min_parallax; int32_t min_triangulated; int32_t gemm_mode;
+    int32_t returned, model, best_h, best_f, n_mot, best_mot;
+    float SH, SF, H21[9], F21[9], R21[9], t21[3], mot_cos[8]; int32_t mot_good[8];
+    uint8_t* mask_h; uint8_t* mask_f; float* p3d; uint8_t* triangulated;
+    float* hyp_score; float* hyp_M; float* mot_R; float* mot_t;
+} orbhip_init_problem;
+orbhip_status orbhip_init_reconstruct(int device, orbhip_init_problem* problem);
+/* independent frame pairs of any mix of sizes in one device call */
+orbhip_status orbhip_init_reconstruct_batch(int device, int nproblems, orbhip_init_problem* problems);
+
 /* ORBmatcher(nnratio, check_ori).SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, window)
    (ORBmatcher.h:69, ORBmatcher.cc:405-520) on host buffers.  The Frame members it reads are passed flat:
    mvKeysUn / mDescriptors of both frames and the image bounds (mnMinX = mnMinY = 0, mnMaxX = im_w,

@@ -19,12 +19,10 @@
 // pose fails every comparison and has 0 inliers.
 #include "orbhip_ctx.h"
 #include "orbhip_jacobi.h"
+#include "orbhip_hestenes.h"
 
 #define PNP_MAX_HYP 4096
 #define PNP_REC 16                     // doubles per record: R[9] t[3] count(int) pad pad pad
-#define PNP_HEST_SWEEPS 30             // sweep bound of the one-sided Jacobi on ABt
-#define PNP_HEST_EPS 1e-15             // a column pair with |g_p . g_q| <= eps sqrt(|g_p|^2 |g_q|^2) is left alone
-#define PNP_RANK_TOL 1e-12             // sigma_3 <= tol sigma_1: ABt has rank 2 (a planar set), the third columns are cross products
 
 struct PnpResult { int n_consumed, returned, best, best_inliers, refined_inliers, n_cand, ok_cand, pad; float best_Tcw[16], refined_Tcw[16]; };
 struct PnpDev {
@@ -162,58 +160,11 @@ __device__ static void pnp_gauss_newton(const double (*L)[10], const double rho[
     }
 }
 
-__device__ __forceinline__ void pnp_rot2(double c, double s, double& xp, double& xq) { const double a = xp, b = xq; xp = c * a - s * b; xq = s * a + c * b; }
-__device__ __forceinline__ void pnp_cross(const double a[3], const double b[3], double o[3])
-{
-    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// R = U V^T of ABt = U S V^T by a one-sided (Hestenes) Jacobi: the columns of G = ABt W are made orthogonal pair by pair, W collects the rotations;
-// singular values are the column norms, sorted descending; then the reference's det < 0 row flip
+// R = U V^T of ABt = U S V^T by the one-sided (Hestenes) Jacobi of orbhip_hestenes.h, then the reference's det < 0 row flip
 __device__ static void pnp_rotation(const double abt[9], double R[9])
 {
-    double G[3][3], W[3][3];      // [column][row]
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int r = 0; r < 3; r++) { G[c][r] = abt[3 * r + c]; W[c][r] = r == c ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < PNP_HEST_SWEEPS; sweep++) {
-        bool rotated = false;
-#pragma unroll
-        for (int pair = 0; pair < 3; pair++) {
-            const int p = pair == 2 ? 1 : 0, q = pair == 0 ? 1 : 2;
-            const double alpha = pnp_dot3(G[p], G[p]), beta = pnp_dot3(G[q], G[q]), gamma = pnp_dot3(G[p], G[q]);
-            if (gamma == 0.0) continue;
-            if (fabs(gamma) <= PNP_HEST_EPS * sqrt(alpha * beta)) continue;
-            rotated = true;
-            const double zeta = (beta - alpha) / (2.0 * gamma);
-            double t;
-            if (fabs(zeta) > 1e150) t = 1.0 / (2.0 * zeta);
-            else { t = 1.0 / (fabs(zeta) + sqrt(zeta * zeta + 1.0)); if (zeta < 0.0) t = -t; }
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-            for (int k = 0; k < 3; k++) { pnp_rot2(c, s, G[p][k], G[q][k]); pnp_rot2(c, s, W[p][k], W[q][k]); }
-        }
-        if (!rotated) break;
-    }
-    double sg[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) sg[c] = sqrt(pnp_dot3(G[c], G[c]));
-    int o0 = 0, o1 = 1, o2 = 2;                                                 // insertion by strict `>`
-    if (sg[o1] > sg[o0]) { const int t = o0; o0 = o1; o1 = t; }
-    if (sg[o2] > sg[o1]) { const int t = o1; o1 = o2; o2 = t; if (sg[o1] > sg[o0]) { const int u = o0; o0 = o1; o1 = u; } }
-    double U[3][3], V[3][3];      // [column][row]
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const int o = c == 0 ? o0 : c == 1 ? o1 : o2;
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const double g = o == 0 ? G[0][r] : o == 1 ? G[1][r] : G[2][r], w = o == 0 ? W[0][r] : o == 1 ? W[1][r] : W[2][r], sv = o == 0 ? sg[0] : o == 1 ? sg[1] : sg[2];
-            U[c][r] = g / sv; V[c][r] = w;
-        }
-    }
-    const double s_first = o0 == 0 ? sg[0] : o0 == 1 ? sg[1] : sg[2], s_third = o2 == 0 ? sg[0] : o2 == 1 ? sg[1] : sg[2];
-    if (!(s_third > PNP_RANK_TOL * s_first)) { pnp_cross(U[0], U[1], U[2]); pnp_cross(V[0], V[1], V[2]); }
+    double U[3][3], V[3][3], sw[3];      // [column][row]
+    orbhip_hestenes3(abt, U, V, sw);
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll

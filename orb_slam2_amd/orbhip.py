@@ -20,7 +20,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
 
 # every symbol include/orbhip.h declares (tests check the library exports all of them)
 SYMBOLS = [
-    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_sim3_iterate", "orbhip_sim3_iterate_batch", "orbhip_pnp_iterate", "orbhip_pnp_iterate_batch", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
+    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_sim3_iterate", "orbhip_sim3_iterate_batch", "orbhip_pnp_iterate", "orbhip_pnp_iterate_batch", "orbhip_init_reconstruct", "orbhip_init_reconstruct_batch", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
     "orbhip_get_scale_tables", "orbhip_level_size", "orbhip_extract", "orbhip_extract_batch", "orbhip_pyramid_level",
     "orbhip_extract_device", "orbhip_sync", "orbhip_fetch", "orbhip_fetch_matches", "orbhip_descriptor_distance",
     "orbhip_hamming_nn", "orbhip_hamming_nn_device", "orbhip_nn_expanded_size", "orbhip_nn_expand_device", "orbhip_hamming_nn_device_expanded", "orbhip_search_for_initialization", "orbhip_profile_enable",
@@ -196,6 +196,8 @@ def lib(path=None):
     L.orbhip_sim3_iterate_batch.argtypes = [C.c_int, C.c_int, vp]
     L.orbhip_pnp_iterate.argtypes = [C.c_int, vp]
     L.orbhip_pnp_iterate_batch.argtypes = [C.c_int, C.c_int, vp]
+    L.orbhip_init_reconstruct.argtypes = [C.c_int, vp]
+    L.orbhip_init_reconstruct_batch.argtypes = [C.c_int, C.c_int, vp]
     L.orbhip_hamming_nn_device.argtypes = [vp, vp, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.orbhip_nn_expanded_size.argtypes = [C.c_int64]; L.orbhip_nn_expanded_size.restype = C.c_size_t
     L.orbhip_nn_expand_device.argtypes = [vp, vp, C.c_int64, vp]
@@ -1149,6 +1151,74 @@ def pnp_iterate_batch(problems, per_hypothesis=False, library=None, device=None,
     else:
         _check(L.orbhip_pnp_iterate_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_pnp_iterate_batch", L)
     return [_pnp_result(arr[k], keep[k]) for k in range(n)]
+
+
+class _InitProblem(C.Structure):                                                # orbhip_init_problem
+    _fields_ = [("K", C.c_float * 4), ("sigma", C.c_float), ("norm1", C.c_float * 4), ("norm2", C.c_float * 4),
+                ("matches", C.c_void_p), ("n", C.c_int32), ("sets", C.c_void_p), ("n_sets", C.c_int32),
+                ("min_parallax", C.c_float), ("min_triangulated", C.c_int32), ("gemm_mode", C.c_int32),
+                ("returned", C.c_int32), ("model", C.c_int32), ("best_h", C.c_int32), ("best_f", C.c_int32), ("n_mot", C.c_int32), ("best_mot", C.c_int32),
+                ("SH", C.c_float), ("SF", C.c_float), ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("R21", C.c_float * 9), ("t21", C.c_float * 3),
+                ("mot_cos", C.c_float * 8), ("mot_good", C.c_int32 * 8),
+                ("mask_h", C.c_void_p), ("mask_f", C.c_void_p), ("p3d", C.c_void_p), ("triangulated", C.c_void_p),
+                ("hyp_score", C.c_void_p), ("hyp_M", C.c_void_p), ("mot_R", C.c_void_p), ("mot_t", C.c_void_p)]
+
+
+def _init_fill(rec, problem, per_hypothesis):
+    """one orbhip_init_problem from a dict; returns the arrays the record points to"""
+    matches = np.ascontiguousarray(problem["matches"], np.float32).reshape(-1, 4)
+    sets = np.ascontiguousarray(problem["sets"], np.int32).reshape(-1, 8)
+    n, ns = len(matches), len(sets)
+    rec.K[:] = [float(v) for v in np.ascontiguousarray(problem["K"], np.float32).reshape(4)]
+    rec.sigma = float(np.float32(problem.get("sigma", 1.0)))
+    rec.norm1[:] = [float(v) for v in np.ascontiguousarray(problem["norm1"], np.float32).reshape(4)]
+    rec.norm2[:] = [float(v) for v in np.ascontiguousarray(problem["norm2"], np.float32).reshape(4)]
+    rec.n, rec.n_sets = n, ns
+    rec.min_parallax, rec.min_triangulated = float(np.float32(problem.get("min_parallax", 1.0))), int(problem.get("min_triangulated", 50))
+    rec.gemm_mode = int(problem.get("gemm_mode", 0))
+    keep = {"matches": matches, "sets": sets, "mask_h": np.zeros(n, np.uint8), "mask_f": np.zeros(n, np.uint8), "p3d": np.zeros((n, 3), np.float32),
+            "triangulated": np.zeros(n, np.uint8)}
+    if per_hypothesis:
+        keep.update(hyp_score=np.zeros((2, ns), np.float32), hyp_M=np.zeros((2, ns, 3, 3), np.float32), mot_R=np.zeros((8, 3, 3), np.float32), mot_t=np.zeros((8, 3), np.float32))
+    for k, a in keep.items():
+        setattr(rec, k, a.ctypes.data if a.size else None)
+    return keep
+
+
+def _init_result(rec, keep):
+    out = {k: int(getattr(rec, k)) for k in ("returned", "model", "best_h", "best_f", "n_mot", "best_mot")}
+    out.update(SH=np.float32(rec.SH), SF=np.float32(rec.SF), H21=np.array(rec.H21[:], np.float32).reshape(3, 3), F21=np.array(rec.F21[:], np.float32).reshape(3, 3),
+               R21=np.array(rec.R21[:], np.float32).reshape(3, 3) if rec.returned else None, t21=np.array(rec.t21[:], np.float32) if rec.returned else None,
+               mot_cos=np.array(rec.mot_cos[:], np.float32), mot_good=np.array(rec.mot_good[:], np.int32),
+               mask_h=keep["mask_h"].astype(bool), mask_f=keep["mask_f"].astype(bool), p3d=keep["p3d"], triangulated=keep["triangulated"].astype(bool))
+    for k in ("hyp_score", "hyp_M", "mot_R", "mot_t"):
+        if k in keep:
+            out[k] = keep[k]
+    return out
+
+
+def init_reconstruct(K, matches, sets, norm1, norm2, sigma=1.0, min_parallax=1.0, min_triangulated=50, gemm_mode=0, per_hypothesis=False, library=None, device=None):
+    """One call of Initializer::Initialize on the device (orbhip_init_reconstruct): K = (fx, fy, cx, cy); matches n x 4 float32 (u1, v1, u2, v2 of
+    pair i in mvMatches12 order); sets n_sets x 8 drawn indices; norm1, norm2 = (meanX, meanY, sX, sY) of Normalize over all key points of each
+    frame.  Returns a dict: returned, model (0 H, 1 F, -1 neither), best_h, best_f, SH, SF, H21, F21, mask_h, mask_f, n_mot, mot_good, mot_cos,
+    best_mot, R21 and t21 (None unless returned), p3d (n x 3) and triangulated (n) per match; with per_hypothesis also hyp_score (2 x n_sets: H, F),
+    hyp_M (2 x n_sets x 3 x 3), mot_R (8 x 3 x 3) and mot_t (8 x 3)."""
+    return init_reconstruct_batch([dict(K=K, matches=matches, sets=sets, norm1=norm1, norm2=norm2, sigma=sigma, min_parallax=min_parallax,
+                                        min_triangulated=min_triangulated, gemm_mode=gemm_mode)], per_hypothesis=per_hypothesis, library=library, device=device, _single=True)[0]
+
+
+def init_reconstruct_batch(problems, per_hypothesis=False, library=None, device=None, _single=False):
+    """Independent frame pairs in one device call (orbhip_init_reconstruct_batch): problems is a sequence of dicts with the keyword names of
+    init_reconstruct.  Returns a list of result dicts."""
+    n = len(problems)
+    arr = (_InitProblem * max(n, 1))()
+    keep = [_init_fill(arr[k], q, per_hypothesis) for k, q in enumerate(problems)]
+    L = lib(library)
+    if _single:
+        _check(L.orbhip_init_reconstruct(0 if device is None else device, C.cast(arr, C.c_void_p)), "orbhip_init_reconstruct", L)
+    else:
+        _check(L.orbhip_init_reconstruct_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_init_reconstruct_batch", L)
+    return [_init_result(arr[k], keep[k]) for k in range(n)]
 
 
 def nn_expanded_size(ndb, library=None):
