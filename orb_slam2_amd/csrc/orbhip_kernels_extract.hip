@@ -16,6 +16,7 @@
 // oracle's two-rounding form.  The one GEMM-shaped piece is the blur (a banded product, exact in i8): it runs on MFMA.
 #include "orbhip_internal.h"
 #include <type_traits>
+#include <utility>
 
 #define WAVE 64
 
@@ -1971,26 +1972,89 @@ __device__ __forceinline__ int round_half_even_small(float x) { return __float_a
                                        // boundary at or below cx - 18), or 12..15 bytes when that would need a third tile column (then staged from 16 bytes into the tile)
 #define DS_PPASS 8                     // orientation patch: 32-bit load passes of 4 rows x 16 lanes
 #define DS_WPASSES 10                  // LDS-DMA passes per window, one TILE ROW each: 4 image rows x 64 bytes = 64 lanes x 4 bytes out of 2 (or 3) 128-byte lines;
-                                       // 10 tile rows hold the 37 rows from any row cy - 18 (16 slots x 2560 B = 40 KB per workgroup, four workgroups per CU)
+                                       // 10 tile rows hold the 37 rows from any row cy - 18: 2560 B per window buffer
 #define DS_WDWORDS (DS_WPASSES * 64)
+#ifndef DS_WRING
+#define DS_WRING 2                     // window buffers per wave: a ring, refilled as slots finish (4 waves x 2 x 2560 B = 20 KB per workgroup, six workgroups per CU with
+                                       // the kernel's <= 80 VGPRs; 3 -> 30 KB and five workgroups; DS_KPW -> every window up front, 40 KB and four: profiles/describe_window_ring.txt)
+#endif
+// One byte of LDS, requested without the compiler's knowledge (as lds_read3_issue above, and for the same reason): the BRIEF reads of one window happen while
+// the LDS-DMA of the NEXT windows is in flight, and as ordinary loads the compiler would guard each of them with s_waitcnt vmcnt(0) - the full latency of the
+// window just requested, once per slot.  The window being read was waited for by count (s_waitcnt vmcnt(n)) in front of the reads.
+__device__ __forceinline__ int lds_read_u8_issue(const uint8_t* p)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    int r;
+    const unsigned a = (unsigned)(unsigned long long)(orbhip_lptr)p;
+    asm volatile("ds_read_u8 %0, %1" : "=&v"(r) : "v"(a));
+    return r;
+#else
+    return *p;
+#endif
+}
+// ... and their wait, which names the eight registers so that nothing that uses them moves in front of it
+__device__ __forceinline__ void lds_read_u8_wait(int (&t0)[4], int (&t1)[4])
+{
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t0[0]), "+v"(t0[1]), "+v"(t0[2]), "+v"(t0[3]), "+v"(t1[0]), "+v"(t1[1]), "+v"(t1[2]), "+v"(t1[3]));
+#endif
+}
+// The orientation patch's dwords, requested without the compiler's knowledge as well.  An LDS-DMA is a FLAT-encoded instruction with an LDS side, and while one
+// is pending the compiler turns every vmcnt wait of its own into vmcnt(0) (it counts a "flat" access as able to complete out of order): the first slot's moment
+// arithmetic then waits for every window behind the patches, although static request counts would let it name the exact count.  So the patch loads and their
+// waits are spelled out: requests return in order, and vm_wait8<N> names the eight registers so that nothing that uses them moves in front of the wait.
+// ("memory": stores in front of the requests stay in front - the counts below are of the requests BEHIND a patch.)
+__device__ __forceinline__ unsigned global_load_u32_issue(const ORBHIP_GLOBAL uint8_t* base, unsigned off)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    unsigned r;
+    asm volatile("global_load_dword %0, %1, %2" : "=&v"(r) : "v"(off), "s"(base) : "memory");
+    return r;
+#else
+    return *reinterpret_cast<const ORBHIP_GLOBAL unsigned*>(base + off);
+#endif
+}
+template <int N> __device__ __forceinline__ void vm_wait8(unsigned (&p)[8])
+{
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    asm volatile("s_waitcnt vmcnt(%8)" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]) : "n"(N));
+#endif
+}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression (a wait's count is an immediate)
+template <class F, int... I> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+// Every LDS read of the wave has returned, and nothing moves across this point: behind it an LDS-DMA may overwrite the bytes that were read
+__device__ __forceinline__ void lds_reads_done()
+{
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
 // One wavefront per DS_KPW consecutive key point slots, in three phases, so that what is per-key-point scalar work in the reference is
 // done once per lane instead of once per wave:
 //   1. IC_Angle (ORBextractor.cc:77-104) of every slot: the 31 x 31 orientation patch as 31 rows x 8 unaligned dwords (4 loads per
 //      lane), circular mask from a table, sum I, sum (u+15) I and row sums by v_dot4_u32_u8, two DPP wave sums; m10 / m01 of slot j
 //      are kept by lane j;
 //   2. cv::fastAtan2 and the glibc sincosf for all slots at once, lane j = slot j;
-//   3. per slot: the 37 x 37 blurred window, brought to LDS by LDS-DMA issued at the very start (one buffer per slot), a and b back by
-//      v_readlane, 256 rotated BRIEF tests whose 4 ballots are the descriptor words.
+//   3. per slot: the 37 x 37 blurred window, brought to LDS by LDS-DMA, a and b back by v_readlane, 256 rotated BRIEF tests whose 4 ballots are
+//      the descriptor words.  A wave owns a ring of RING window buffers: the windows of its first RING slots are requested at the very start, and
+//      when slot k's BRIEF reads have returned the window of slot k + RING is requested into the buffer slot k used - LDS is held only while a window
+//      is needed, so more waves are resident.  Every wait is counted by hand; the counts are static because an invalid slot requests the patch and
+//      the window of the wave's first valid slot (in bounds, the same lines) instead of nothing.
 // The rBRIEF pattern, the mask and the DMA layout are loaded / computed once per wave.
+template <int RING>
 __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
 {
-    __shared__ unsigned s_win[DS_WAVES][DS_KPW][DS_WDWORDS];
+    static_assert(RING >= 1 && RING <= DS_KPW, "ring depth");
+    __shared__ unsigned s_win[DS_WAVES][RING][DS_WDWORDS];
     // the rBRIEF pattern (4 KB, [component][round][lane]) is fetched once per workgroup with four coalesced 32-bit loads per thread - as 16-byte
     // loads per lane it cost every wave 4 x 71 cycles of the texture addresser, more than the wave's orientation patches (tools/ta_ubench.hip) -
     // and passes through the first window buffers on its way to the lanes' registers (two barriers, before any wave leaves or stages a window):
-    // the workgroup's LDS stays the windows' 40 KB
+    // the workgroup's LDS stays the windows'
     float* s_pat = reinterpret_cast<float*>(&s_win[0][0][0]);
-    static_assert(DS_KPW * DS_WDWORDS >= 16 * 64, "the pattern passes through wave 0's window buffers");
+    static_assert(RING * DS_WDWORDS >= 16 * 64, "the pattern passes through wave 0's ring of window buffers");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     // A workgroup's start is a chain of memory latencies (pattern -> LDS -> barriers, slot metadata, orientation patches), and a wave lives for
     // only ~11 us: the pattern, the metadata and the circle mask are requested together, and the patch loads are issued BEFORE the pattern's
@@ -2049,25 +2113,31 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
         if (live && lane < DS_KPW && slot0 + lane < P.lvl_kp_per_frame && i < nsel && obase + i < P.out_cap) myOi = obase + i;
     }
     bool ok[DS_KPW]; int lv[DS_KPW], oi[DS_KPW]; unsigned vv[DS_KPW];
-    int oi_first = -1;
+    int oi_first = -1, lv_first = 0; unsigned vv_first = 0;
 #pragma unroll
     for (int j = 0; j < DS_KPW; j++) {
         oi[j] = RL(myOi, j); lv[j] = RL(myLevel, j); vv[j] = (unsigned)RL((int)myV, j);
         ok[j] = oi[j] >= 0;
-        if (ok[j] && oi_first < 0) oi_first = oi[j];
+        if (ok[j] && oi_first < 0) { oi_first = oi[j]; lv_first = lv[j]; vv_first = vv[j]; }
     }
+    // an invalid slot requests what the wave's first valid slot requests: every wave with a valid slot issues the same number of requests in the same
+    // order, so that "this one has landed" is a constant for s_waitcnt vmcnt (requests return in order) and no count is merged to 0 at a join
+#pragma unroll
+    for (int j = 0; j < DS_KPW; j++) if (!ok[j]) { lv[j] = lv_first; vv[j] = vv_first; }
     // the orientation patches of the wave's slots: requested here, in front of the pattern's barriers
     unsigned pw[DS_KPW][DS_PPASS];
+    if (oi_first >= 0) {                                                   // (a wave without a valid slot requests nothing and leaves behind the barriers)
 #pragma unroll
-    for (int j = 0; j < DS_KPW; j++) if (ok[j]) {
-        const int spitch = lv[j] == 0 ? P.img0_pitch : RL(g_pitch, lv[j]);
-        const ORBHIP_GLOBAL uint8_t* img = uniform_ptr(lv[j] == 0 ? P.img0 + (long long)frame * P.img0_frame_stride
-                                                                  : P.pyr + (long long)frame * P.plane_frame_bytes + RL(g_poff, lv[j]));
-        const int cx = vv[j] & 0xfff, cy = (vv[j] >> 12) & 0xfff;
-        const unsigned off = (unsigned)((cy - 15 + prow) * spitch + ((cx - 15) & ~3) + 4 * min(pd, 8));
+        for (int j = 0; j < DS_KPW; j++) {
+            const int spitch = lv[j] == 0 ? P.img0_pitch : RL(g_pitch, lv[j]);
+            const ORBHIP_GLOBAL uint8_t* img = uniform_ptr(lv[j] == 0 ? P.img0 + (long long)frame * P.img0_frame_stride
+                                                                      : P.pyr + (long long)frame * P.plane_frame_bytes + RL(g_poff, lv[j]));
+            const int cx = vv[j] & 0xfff, cy = (vv[j] >> 12) & 0xfff;
+            const unsigned off = (unsigned)((cy - 15 + prow) * spitch + ((cx - 15) & ~3) + 4 * min(pd, 8));
 #pragma unroll
-        for (int q = 0; q < DS_PPASS; q++)                             // rows prow + 4q - 15 = -15 .. 16; row 16 is loaded (in bounds) and masked
-            pw[j][q] = *reinterpret_cast<const ORBHIP_GLOBAL unsigned*>(img + (off + (unsigned)(4 * q * spitch)));
+            for (int q = 0; q < DS_PPASS; q++)                         // rows prow + 4q - 15 = -15 .. 16; row 16 is loaded (in bounds) and masked
+                pw[j][q] = global_load_u32_issue(img, off + (unsigned)(4 * q * spitch));
+        }
     }
     __syncthreads();
     float4 pt[4];                                                          // rBRIEF pattern of this lane's 4 tests as floats (x0, y0, x1, y1)
@@ -2076,8 +2146,9 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
     __syncthreads();                                                       // (behind it the window buffers are the windows')
     if (oi_first < 0) return;
 
-    // ---- 1. IC_Angle of every slot.  Every memory request of the wave is issued here, before anything is waited for: the patch loads of
-    //      all slots, then the LDS-DMA of all blurred windows (one LDS buffer per slot) - a wave pays the memory latency once
+    // ---- 1. IC_Angle of every slot.  The patch loads of all slots are out; behind them go the LDS-DMA of the first RING blurred windows, before
+    //      anything is waited for.  Outstanding: 8 x DS_KPW + DS_WPASSES x RING requests (52 at depth 2: inside the 6-bit vmcnt), so slot j's patch
+    //      has landed at vmcnt(DS_WPASSES x RING + 8 x (DS_KPW - 1 - j)): a constant, because no request is conditional
     // The blurred plane is stored as 32x4 tiles, one 128-byte line each (orbhip_blur_tile_addr): a pass is one tile row of the window and touches two lines,
     // three when (cx - 18) & 31 > 27 - against 5 to 6 rows of 48 bytes, a line each, in a row-major plane (tools/window_gather_probe.hip).  The span's first
     // tile goes into the scalar pointer, which moves on by one tile row per pass; the window lands row-major with a 64-byte stride.
@@ -2095,10 +2166,15 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
     int M10 = 0, M01 = 0;
     {
 #pragma unroll
-        for (int j = 0; j < DS_KPW; j++) if (ok[j]) window_dma(lv[j], vv[j], s_win[wave][j]);
-#pragma unroll
-        for (int j = 0; j < DS_KPW; j++) if (ok[j]) {
-            unsigned s = 0, su = 0, cs = 0;                                   // cs = sum over passes of the running row sum = sum_q (8 - q) t_q
+        for (int j = 0; j < RING; j++) window_dma(lv[j], vv[j], s_win[wave][j]);
+        static_for<DS_KPW>([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            // behind slot j's patch: the patches of the slots after it and the first RING windows (44, 36, 28, 20 at depth 2).  The wait is made for an invalid
+            // slot too: its registers are the target of requests until it has passed.  (With every window up front there are 72 requests; the counter holds 63.)
+            constexpr int behind = DS_WPASSES * RING + DS_PPASS * (DS_KPW - 1 - j);
+            vm_wait8<(behind < 63 ? behind : 63)>(pw[j]);
+            if (!ok[j]) return;
+            unsigned s = 0, su = 0, cs = 0;                                  // cs = sum over passes of the running row sum = sum_q (8 - q) t_q
             const unsigned sh = (unsigned)((vv[j] & 0xfff) - 15) & 3u;        // (cx - 15) & 3: byte 0 of the shifted dword is column cx - 15 + 4 pd
 #pragma unroll
             for (int q = 0; q < DS_PPASS; q++) {
@@ -2112,7 +2188,7 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
             const int sv = (prow + 17) * (int)s - 4 * (int)cs;
             const int m10 = wave_sum_dpp((int)su - 15 * (int)s), m01 = wave_sum_dpp(sv);     // sum u*I, sum v*I (wave-uniform)
             if (lane == j) { M10 = m10; M01 = m01; }
-        }
+        });
     }
 
     // ---- 2. orientation and its sine / cosine, lane j = slot j
@@ -2124,23 +2200,23 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
     //      is collected in lane 4k + r, so nothing is stored (and no store is waited for) inside the loop
     int dlo_l = 0, dhi_l = 0;                                               // the 64-bit word as two registers: v_writelane_b32 drops a wave-uniform value into one lane
     {
-        int later = 0;                                                      // valid slots behind slot j: their windows' loads are the youngest outstanding ones
-#pragma unroll
-        for (int j = 0; j < DS_KPW; j++) later += ok[j] ? 1 : 0;
 #pragma unroll
         for (int j = 0; j < DS_KPW; j++) {
-            if (!ok[j]) continue;
-            later--;
-            // vmcnt counts in order: at most DS_WPASSES * later loads outstanding  <=>  this slot's window (and everything older) has landed
+            // vmcnt counts in order.  When slot j starts, the windows of slots 0 .. min(j + RING, DS_KPW) - 1 have been requested: at most DS_WPASSES x
+            // (windows requested behind this one) loads outstanding  <=>  this slot's window (and everything older) has landed.  Depth 2: 10, 10, 10, 0
+            // (3 x 10, 2 x 10, 10, 0 with every window up front).  The last slot's wait is the only one for everything, and it is made for an invalid
+            // slot too: a wave ends with no request in flight towards LDS that another workgroup may own by then.
+            const int later = (j + RING < DS_KPW ? j + RING : DS_KPW) - 1 - j;          // (a constant once the loop is unrolled)
             if (later >= 3) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(3 * DS_WPASSES));
             else if (later == 2) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(2 * DS_WPASSES));
             else if (later == 1) __builtin_amdgcn_s_waitcnt(ORBHIP_VMCNT(DS_WPASSES));
             else lds_dma_wait();
             __builtin_amdgcn_wave_barrier();
+            if (ok[j]) {
             const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a_l), j)), b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b_l), j));
             // key point position inside the window: its first row is row (cy - 18) & 3 of the first tile row, its first column sits (cx - 18) & 31 bytes behind the tile boundary, less the 16 of the three-tile span
             const int wx0 = (int)(vv[j] & 0xfff) - 18, wy0 = (int)((vv[j] >> 12) & 0xfff) - 18;
-            const uint8_t* w8 = reinterpret_cast<const uint8_t*>(s_win[wave][j]) + (18 + (wy0 & 3)) * DS_WSTRIDE + 18 + ((wx0 & 31) > 27 ? (wx0 & 15) : (wx0 & 31));
+            const uint8_t* w8 = reinterpret_cast<const uint8_t*>(s_win[wave][j % RING]) + (18 + (wy0 & 3)) * DS_WSTRIDE + 18 + ((wx0 & 31) > 27 ? (wx0 & 15) : (wx0 & 31));
             const int dlane = 4 * (oi[j] - oi_first);
             // P.fp_contract (wave-uniform): 0 = x*b + y*a as two roundings (a build with -ffp-contract=off, H3), 1 = the fused forms gcc emits
             // for the reference's own flags, fma(x, b, y*a) and fma(x, a, -(y*b))
@@ -2171,10 +2247,11 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
                     const f2v ry = fy + MG, rx = fx + MG;
                     const int o0 = (int)((__float_as_uint(ry[0]) << 6) + __float_as_uint(rx[0]) - cbias);
                     const int o1 = (int)((__float_as_uint(ry[1]) << 6) + __float_as_uint(rx[1]) - cbias);
-                    t0[r] = w8[o0]; t1[r] = w8[o1];
+                    t0[r] = lds_read_u8_issue(w8 + o0); t1[r] = lds_read_u8_issue(w8 + o1);
                 }
                 // all eight byte reads are out before the first comparison: with the ballots and v_writelane (an asm statement: a scheduling boundary) in the
                 // same loop, every round waited for its own two reads - eight LDS round trips per slot one after the other (round 5)
+                lds_read_u8_wait(t0, t1);
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const unsigned long long bits = __ballot(t0[r] < t1[r]);       // test 64r+lane -> byte (64r+lane)/8, bit lane%8
@@ -2183,7 +2260,11 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
                 }
             };
             if (P.fp_contract) brief(std::true_type{}); else brief(std::false_type{});
+            }
             __builtin_amdgcn_wave_barrier();
+            // the buffer is free: the window of slot j + RING goes into it.  An LDS-DMA must never overwrite bytes that a read still wants, so the request
+            // stands behind an explicit wait for this slot's byte reads and a scheduling barrier
+            if (j + RING < DS_KPW) { lds_reads_done(); window_dma(lv[j + RING], vv[j + RING], s_win[wave][j % RING]); }
         }
     }
     // ---- outputs: the wave's descriptors are one contiguous run of 8-byte words, its key point records one per lane
@@ -2209,5 +2290,10 @@ __global__ __launch_bounds__(256) void k_describe(ExtractParams P)
 void orbhip_launch_describe(const ExtractParams& P, int nframes, hipStream_t s)
 {
     ExtractParams Q = P; Q.nframes = nframes;
-    hipLaunchKernelGGL(k_describe, dim3(xcd_grid((P.lvl_kp_per_frame + DS_WAVES * DS_KPW - 1) / (DS_WAVES * DS_KPW), nframes), 1, 1), dim3(256, 1, 1), 0, s, Q);
+    // Up to eight frames (the drop-in's single-image call: at most one workgroup per CU) there are no other waves to hide a refill's latency behind: every window
+    // up front, as before the ring, with the counted waits.  Larger batches: the ring, for the resident waves its smaller LDS allows.
+    int ring = nframes <= 8 ? DS_KPW : DS_WRING;
+    { const char* e = getenv("ORBHIP_TEST_DESCRIBE_RING"); if (e && *e) ring = atoi(e); }      // tests: 2, 3 or 4 = every window up front (read per call: tests switch inside one process)
+    auto kernel = ring == 2 ? k_describe<2> : ring == 3 ? k_describe<3> : k_describe<DS_KPW>;
+    hipLaunchKernelGGL(kernel, dim3(xcd_grid((P.lvl_kp_per_frame + DS_WAVES * DS_KPW - 1) / (DS_WAVES * DS_KPW), nframes), 1, 1), dim3(256, 1, 1), 0, s, Q);
 }
