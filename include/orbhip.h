@@ -294,6 +294,31 @@ orbhip_status orbhip_sim3_iterate(int device, orbhip_sim3_problem* problem);
 /* one round of LoopClosing::ComputeSim3's candidate loop: independent solvers of any mix of sizes */
 orbhip_status orbhip_sim3_iterate_batch(int device, int nproblems, orbhip_sim3_problem* problems);
 
+/* Optimizer::OptimizeSim3 (Optimizer.cc:1046-1241): one free Sim(3) vertex S12 against n matched map-point pairs, as g2o runs it there - for every pair
+   a forward edge (X2 through S12 into camera 1, against (u1, v1)) and an inverse edge (X1 through S12^-1 into camera 2, against (u2, v2)), Huber kernel
+   of delta (float)sqrt(th2) on both, NUMERICAL Jacobians (central differences, step 1e-9, as g2o forms them for these two edge types), optimize(5),
+   removal of every pair with either chi2 > th2, then optimize(10) if a pair was removed and optimize(5) otherwise, and the second check.
+   X1 = R1w P3D1w + t1w and X2 = R2w P3D2w + t2w are the FLOAT camera-frame points as the member computes them; inv_sigma2 is mvInvLevelSigma2[octave].
+   S12_in / S12_out are qx qy qz qw tx ty tz s in double; the quaternion is taken as given (g2o::Sim3 does not normalise it) and comes out unnormalised.
+   removed[i] = 1 exactly where the member sets vpMatches1[idx] = NULL, after either check; n_inliers is its return value.  Where the member returns 0
+   early (fewer than 10 pairs left after the first check; always with n < 10) removed holds the first check's flags, n_inliers = 0 and S12_out = S12_in
+   bit for bit.  n == 0: ORBHIP_OK, n_inliers = 0, nothing else written.  fix_scale: the scale comes out with the bits it came in with.
+   One upload, one launch and one download per call, all problems of a batch in the same launch; results repeat bit for bit and do not depend on a
+   problem's place in a batch.  Re-entrant like the pose-optimisation entries. */
+typedef struct { float u1, v1, inv_sigma2_1;      /* pKF1->mvKeysUn[i], mvInvLevelSigma2[octave] */
+                 float u2, v2, inv_sigma2_2;      /* pKF2->mvKeysUn[i2] */
+                 float X1[3];                     /* P3D1c = R1w*P3D1w + t1w, the float the caller computed */
+                 float X2[3]; } orbhip_sim3_pair; /* P3D2c */
+typedef struct { float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2; } orbhip_sim3_cameras;
+typedef struct {
+    orbhip_sim3_cameras cam; double S12_in[8];    /* qx qy qz qw tx ty tz s - as given, NOT normalised */
+    const orbhip_sim3_pair* pairs; int32_t n; float th2; int32_t fix_scale;
+    double S12_out[8]; uint8_t* removed /* n */; int32_t n_inliers;
+} orbhip_sim3_opt_problem;
+orbhip_status orbhip_sim3_optimize(int device, orbhip_sim3_opt_problem* problem);
+/* one round of LoopClosing::ComputeSim3's accepted candidates: independent problems of any mix of sizes */
+orbhip_status orbhip_sim3_optimize_batch(int device, int nproblems, orbhip_sim3_opt_problem* problems);
+
 /* PnPsolver::iterate (PnPsolver.cc:165-258): relocalisation's RANSAC over n 3-D to 2-D correspondences of one frame and one candidate key frame.
    The caller draws the minimal sets (`quads`: 4 indices per hypothesis, each in 0..n-1 and distinct within a quadruple, as the solver's swap-remove
    draw gives them); the device solves EPnP for every hypothesis (compute_pose), counts its inliers (CheckInliers), replays the loop over the counts in

@@ -20,7 +20,7 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
 
 # every symbol include/orbhip.h declares (tests check the library exports all of them)
 SYMBOLS = [
-    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_sim3_iterate", "orbhip_sim3_iterate_batch", "orbhip_pnp_iterate", "orbhip_pnp_iterate_batch", "orbhip_init_reconstruct", "orbhip_init_reconstruct_batch", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
+    "orbhip_version", "orbhip_thread_release", "orbhip_thread_api_ms", "orbhip_distinctive_descriptors", "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_pose_optimization_frame", "orbhip_sim3_iterate", "orbhip_sim3_iterate_batch", "orbhip_sim3_optimize", "orbhip_sim3_optimize_batch", "orbhip_pnp_iterate", "orbhip_pnp_iterate_batch", "orbhip_init_reconstruct", "orbhip_init_reconstruct_batch", "orbhip_device_count", "orbhip_last_error", "orbhip_create", "orbhip_destroy", "orbhip_keypoint_capacity",
     "orbhip_get_scale_tables", "orbhip_level_size", "orbhip_extract", "orbhip_extract_batch", "orbhip_pyramid_level",
     "orbhip_extract_device", "orbhip_sync", "orbhip_fetch", "orbhip_fetch_matches", "orbhip_descriptor_distance",
     "orbhip_hamming_nn", "orbhip_hamming_nn_device", "orbhip_nn_expanded_size", "orbhip_nn_expand_device", "orbhip_hamming_nn_device_expanded", "orbhip_search_for_initialization", "orbhip_profile_enable",
@@ -194,6 +194,8 @@ def lib(path=None):
     L.orbhip_pose_optimization_frame.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.orbhip_sim3_iterate.argtypes = [C.c_int, vp]
     L.orbhip_sim3_iterate_batch.argtypes = [C.c_int, C.c_int, vp]
+    L.orbhip_sim3_optimize.argtypes = [C.c_int, vp]
+    L.orbhip_sim3_optimize_batch.argtypes = [C.c_int, C.c_int, vp]
     L.orbhip_pnp_iterate.argtypes = [C.c_int, vp]
     L.orbhip_pnp_iterate_batch.argtypes = [C.c_int, C.c_int, vp]
     L.orbhip_init_reconstruct.argtypes = [C.c_int, vp]
@@ -1073,6 +1075,54 @@ def sim3_iterate_batch(problems, per_hypothesis=False, device=None, library=None
     else:
         _check(L.orbhip_sim3_iterate_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_sim3_iterate_batch", L)
     return [_sim3_result(arr[k], keep[k]) for k in range(n)]
+
+
+SIM3_PAIR_DTYPE = np.dtype([("u1", "<f4"), ("v1", "<f4"), ("inv_sigma2_1", "<f4"), ("u2", "<f4"), ("v2", "<f4"), ("inv_sigma2_2", "<f4"), ("X1", "<f4", 3), ("X2", "<f4", 3)])     # orbhip_sim3_pair
+
+
+class _Sim3OptProblem(C.Structure):                                             # orbhip_sim3_opt_problem
+    _fields_ = [("cam", C.c_float * 8), ("S12_in", C.c_double * 8), ("pairs", C.c_void_p), ("n", C.c_int32), ("th2", C.c_float), ("fix_scale", C.c_int32),
+                ("S12_out", C.c_double * 8), ("removed", C.c_void_p), ("n_inliers", C.c_int32)]
+
+
+def _sim3_pairs(pairs):
+    pairs = np.asarray(pairs)
+    return np.ascontiguousarray(pairs if pairs.dtype == SIM3_PAIR_DTYPE else np.ascontiguousarray(pairs, np.float32).reshape(-1, 12).view(SIM3_PAIR_DTYPE).reshape(-1))
+
+
+def sim3_optimize(cams, S12, pairs, th2=10.0, fix_scale=False, device=None, library=None):
+    """Optimizer::OptimizeSim3 on the device (orbhip_sim3_optimize): cams = (fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2); S12 = (qx, qy, qz, qw, tx, ty, tz, s)
+    float64, the quaternion taken as given; pairs an array of SIM3_PAIR_DTYPE (or n x 12 float32: u1, v1, inv_sigma2_1, u2, v2, inv_sigma2_2, X1c, X2c).
+    Returns (S12_out float64[8], removed uint8[n], n_inliers); where the member returns 0 early S12_out is S12."""
+    return sim3_optimize_batch([(cams, S12, pairs, th2, fix_scale)], device=device, library=library, _single=True)[0]
+
+
+def sim3_optimize_batch(problems, device=None, library=None, _single=False):
+    """Independent problems in one device call (orbhip_sim3_optimize_batch): problems is a sequence of (cams, S12, pairs[, th2[, fix_scale]]) as
+    sim3_optimize takes them.  Returns a list of (S12_out, removed, n_inliers)."""
+    n = len(problems)
+    arr = (_Sim3OptProblem * max(n, 1))()
+    keep = []
+    for k, q in enumerate(problems):
+        cams, S12, pairs = q[:3]
+        pairs = _sim3_pairs(pairs)
+        removed = np.zeros(len(pairs), np.uint8)
+        keep.append((pairs, removed))
+        Sin = np.ascontiguousarray(S12, np.float64).reshape(8)
+        C.memmove(arr[k].cam, np.ascontiguousarray(cams, np.float32).reshape(8).ctypes.data, 32)
+        C.memmove(arr[k].S12_in, Sin.ctypes.data, 64)
+        C.memmove(arr[k].S12_out, Sin.ctypes.data, 64)
+        arr[k].pairs = pairs.ctypes.data if len(pairs) else None
+        arr[k].n = len(pairs)
+        arr[k].th2 = float(np.float32(q[3] if len(q) > 3 else 10.0))
+        arr[k].fix_scale = int(bool(q[4])) if len(q) > 4 else 0
+        arr[k].removed = removed.ctypes.data if len(pairs) else None
+    L = lib(library)
+    if _single:
+        _check(L.orbhip_sim3_optimize(0 if device is None else device, C.cast(arr, C.c_void_p)), "orbhip_sim3_optimize", L)
+    else:
+        _check(L.orbhip_sim3_optimize_batch(0 if device is None else device, n, C.cast(arr, C.c_void_p)), "orbhip_sim3_optimize_batch", L)
+    return [(np.frombuffer(bytes(arr[k].S12_out), np.float64).copy(), keep[k][1], int(arr[k].n_inliers)) for k in range(n)]
 
 
 PNP_CORR_DTYPE = np.dtype([("Xw", "<f4", 3), ("u", "<f4"), ("v", "<f4"), ("max_error", "<f4")])                                                  # orbhip_pnp_corr
